@@ -10,11 +10,29 @@ thread merges the pools waiting for predictions into segmented launches of the f
 Games shard across ranks by global game index (no data-path collective); RCCL is used only to
 broadcast the weight blob from rank 0 (the generation-roll hook) before timing.
 
-Steady state.  Every game starts from the initial position, and what a leaf costs the host depends
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline figure needs:
+set up, W warmup steps, K timed steps, the outputs if --dump-outputs is given, the JSON line.  It
+starts every game from the initial position, so its window is the opening phase.  Everything else
+the bench measures is behind --full: the aged (steady-state) window described below with the
+opening-phase rate read during it, and the CPU baseline.  --age-seconds / --age-games given
+explicitly age a plain run too.
+
+--dump-outputs DIR writes, after the timed steps, one launch of the timed path's form: the planes
+of the merged pools in, their policies and values out (planes.npy, policy_<i>.npy, value.npy,
+float32, rows in pool order).  The runner's own launches are composed by timing, so they cannot be
+compared between runs; but every pool's trajectory is fixed by the seed, the weights and the
+network's outputs.  So after the runner stopped, the run's first pools -- as many as the launcher
+waits for (--min-launch-rows), at least enough for the large-launch trunk kernel -- are replayed
+in lockstep on the runner's network, each round one gz_net_forward_segments launch as the runner
+issues them (HBM staging, a segment per pool, outputs into pinned host memory), up to the batch the
+run's W + K steps reach on average (at most DUMP_MAX_POLLS); the last launch is written.  Same
+arguments, same inputs: two builds can be compared array for array.
+
+Steady state (--full).  Every game starts from the initial position, and what a leaf costs the host depends
 on the game phase (endgames spin through up to millions of NN-free playouts per move), so a
-window right after the start measures the opening only, and no game completes in it.  The bench
+window right after the start measures the opening only, and no game completes in it.  With --full the bench
 therefore first AGES the game population: it runs self-play until --age-games completed games per
-game slot (default 3.0) or --age-seconds (default 400) elapse.  The population starts in lockstep
+game slot (default 3.0) or --age-seconds (default 400 with --full) elapse.  The population starts in lockstep
 and the endgames' share of the host's time keeps growing for several generations: the 660-s curve
 of this configuration (profiles/r03p_steady_curve.log) falls from 1.33 M leaf-evals/s at one game
 per slot (120 s, the round-2 window) to ~1.04 M at three (360 s) and ~0.95 M at five (600 s), so
@@ -143,7 +161,7 @@ def per_game_cost(o, threads, slots, run_s, rate=None, world=1):
                             if o["inflight_engine_s"] > 0 else None}}
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -151,7 +169,14 @@ def parse():
     ap.add_argument("--step-rows", type=int, default=1 << 19, help="leaf evaluations per step per rank")
     ap.add_argument("--age-games", type=float, default=3.0,
                     help="steady state: age the game population until this many games per game slot completed ...")
-    ap.add_argument("--age-seconds", type=float, default=400.0, help="... or this many seconds passed (0: no aging)")
+    ap.add_argument("--age-seconds", type=float, default=None,
+                    help="... or this many seconds passed (0: no aging; default 400 with --full, else 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the aged steady-state window (--age-seconds 400), "
+                         "the opening-phase rate and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps replay the run's first pools in merged launches of the runner's form "
+                         "and write the last launch's planes, policies and values as DIR/<name>.npy (float32)")
     ap.add_argument("--threads", type=int, default=0, help="engine threads per GPU (0: the rank's CPU share)")
     ap.add_argument("--pools", type=int, default=2, help="game pools per engine thread")
     ap.add_argument("--batch", type=int, default=256)
@@ -169,7 +194,7 @@ def parse():
     ap.add_argument("--opening-seconds", type=float, default=30.0,
                     help="also report the GPU leg's rate over the first seconds of aging (the opening phase the "
                          "CPU baseline measures)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--seed", type=int, default=20251015)
     ap.add_argument("--min-launch-rows", type=int, default=1024,
                     help="hold a launch until this many rows are queued ...")
@@ -181,7 +206,14 @@ def parse():
                          "(RCCL broadcast) and replaces the live runner's network (gz_runner_update_network)")
     ap.add_argument("--spin-yield", type=int, default=1000,
                     help="yield a game's coroutine after this many NN-free playouts (0: reference behaviour)")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.age_seconds is None:
+        args.age_seconds = 400.0 if args.full else 0.0
+    args.cpu_baseline = args.full and not args.no_cpu_baseline
+    if args.dump_outputs and args.roll:
+        # the replay would play the pools' first batches on the second generation's weights
+        ap.error("--dump-outputs replays the pools from their first batch on one network: not with --roll")
+    return args
 
 
 def selfplay_conf(mode, evals):
@@ -268,6 +300,73 @@ def cpu_baseline(seconds, evals, mode, batch, config=2):
                       "of the reference's worker-thread design (%d C++ worker threads x 2 pools x %d games, "
                       "Supervisor.poll loop) with a float32 torch-CPU network on %d threads"
                       % (el, sm.game, evals, mode, workers, batch, cores)}
+
+
+DUMP_MAX_POLLS = 1024          # --dump-outputs: rounds replayed (4 ms each at 4 x 256 games; 800 evals/move: the second move)
+
+
+def dump_polls(args, games_per_rank):
+    """The batch number --dump-outputs stops at: a pool's batch count when the run's warmup + timed
+    steps end (every batch advances each of the pool's games by one evaluation), capped."""
+    return max(1, min(DUMP_MAX_POLLS, (args.warmup + args.steps) * args.step_rows // games_per_rank))
+
+
+def dump_pools(args, num_pools, large_min_rows, max_segments):
+    """The pools --dump-outputs replays and merges into each launch: as many of the run's pools as
+    the launcher waits for (--min-launch-rows), at least enough for the large-launch trunk kernel."""
+    want = -(-max(args.min_launch_rows, large_min_rows) // args.batch)
+    return max(1, min(num_pools, max_segments, want))
+
+
+def dump_outputs(path, net, sm, transformer, conf, batch, seed, game_base, pools, polls):
+    """--dump-outputs: the runner's first `pools` game pools (gz_runner_create: seed, game_index_base
+    + i * batch, each its own duplicate filter) polled in lockstep from here on the runner's network.
+    Every round is one launch in the runner's form (runner.hip): the pools' planes copied into one
+    HBM staging buffer, one gz_net_forward_segments launch with a segment per pool, policies and
+    values written by the kernel into pinned host buffers.  Writes the last launch (round `polls`):
+    the planes handed over and the policies / values that came back, rows in pool order."""
+    import numpy as np
+    import torch
+    from galvanise_zero_amd.runner import GamePool
+    t = transformer
+    sizes, row = list(t.policy_dist_count) + [t.num_rewards], t.num_channels * t.num_cols * t.num_rows
+    gp = [GamePool(sm, t, conf, batch, identifier="dump_p%d" % i, seed=seed, game_index_base=game_base + i * batch)
+          for i in range(pools)]
+    h_planes = torch.empty((pools * batch, row), dtype=torch.float32).pin_memory()
+    d_planes = torch.empty((pools * batch, row), dtype=torch.float32, device="cuda")
+    h_out = [[torch.empty((batch, k), dtype=torch.float32).pin_memory() for k in sizes] for _ in gp]
+    stream = torch.cuda.current_stream()
+    n, rows = [0] * pools, 0
+    for _ in range(polls):
+        segs, r0 = [], 0
+        for i, g in enumerate(gp):
+            n[i] = g.poll(n[i])                     # (n[i] <= batch: the buffers' rows)
+            if n[i]:
+                h_planes[r0:r0 + n[i]] = torch.from_numpy(g.planes[:n[i]].reshape(n[i], row))
+                segs.append((n[i], d_planes.data_ptr() + r0 * row * 4, [o.data_ptr() for o in h_out[i][:-1]],
+                             h_out[i][-1].data_ptr()))
+                r0 += n[i]
+        if not segs:
+            continue
+        rows = r0
+        d_planes[:rows].copy_(h_planes[:rows], non_blocking=True)
+        net.forward_segments(stream.cuda_stream, segs)
+        stream.synchronize()
+        for i, g in enumerate(gp):
+            for dst, src in zip(g.policies + [g.values], h_out[i]):
+                dst[:n[i]] = src[:n[i]].numpy()
+    for g in gp:
+        g.close()
+    if rows == 0:
+        raise RuntimeError("--dump-outputs: the pools produced no batch in %d polls" % polls)
+    names = ["policy_%d" % k for k in range(len(sizes) - 1)] + ["value"]
+    arrays = {"planes": h_planes[:rows].numpy().reshape(rows, t.num_channels, t.num_cols, t.num_rows)}
+    for k, name in enumerate(names):
+        arrays[name] = np.concatenate([h_out[i][k][:n[i]].numpy() for i in range(pools) if n[i]])
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return rows, {name: list(a.shape) for name, a in arrays.items()}
 
 
 def launch_ranks(args):
@@ -408,7 +507,7 @@ def main():
               file=sys.stderr, flush=True)
 
     runner.start()
-    # ---- aging: until the population has turned over (or the time limit) ----------------------
+    # ---- aging (--full, or --age-seconds given): until the population has turned over (or the time limit)
     # the first --opening-seconds of it are also reported as the opening-phase rate (the phase the
     # CPU baseline runs in)
     age_target = args.age_games * games_per_rank
@@ -547,7 +646,8 @@ def main():
             "selfplay_counters": {"games_completed": games, "no_sample_games": no_samples, "resigns": resigns,
                                   "aborts": aborts, "duplicate_states": dupes},
             "nn_free_playouts_per_leaf": (tree_playouts - rows) / rows if rows else None,
-            "steady_state": {"aging_s": age_s, "games_completed_before_window": aged_games,
+            "full": args.full,
+            "steady_state": {"aged": args.age_seconds > 0, "aging_s": age_s, "games_completed_before_window": aged_games,
                              "games_per_slot_before_window": aged_games / games_total if games_total else None,
                              "age_games_target": args.age_games, "age_seconds_limit": args.age_seconds},
             "n_gpus": world,
@@ -622,7 +722,8 @@ def main():
     # of the timed steps.  The stop is bounded (gz_runner_stop cancels the pools: an engine thread
     # inside a long NN-free root spin returns at the game's next playout); its time goes in the line
     # when the line is printed after it.
-    line_first = rank == 0 and (world > 1 or args.no_cpu_baseline)
+    # (the line also waits for the stop when it reports work done after it: the dump, the CPU baseline)
+    line_first = rank == 0 and not args.dump_outputs and (world > 1 or not args.cpu_baseline)
     if line_first:
         print(json.dumps(out), flush=True)
     t_stop = time.time()
@@ -630,8 +731,20 @@ def main():
     if rank == 0:   # (only rank 0 builds the line)
         out["runner_stop_s"] = time.time() - t_stop
     runner.close()   # frees the games' trees before the CPU baseline
+    if rank == 0 and args.dump_outputs:
+        from galvanise_zero_amd._native import GZ_MAX_SEGMENTS
+        polls = dump_polls(args, games_per_rank)
+        pools = dump_pools(args, threads * args.pools, net.large_min_rows(), GZ_MAX_SEGMENTS)
+        t_dump = time.time()
+        rows, shapes = dump_outputs(args.dump_outputs, net, sm, transformer, selfplay_conf(args.mode, evals),
+                                    args.batch, args.seed, game_base, pools, polls)
+        out["dump_outputs"] = {"dir": args.dump_outputs, "pools": pools, "batch": polls, "launch_rows": rows,
+                               "large_min_rows": net.large_min_rows(),
+                               "kernel": net.kernel_name(rows >= net.large_min_rows()),
+                               "arrays": shapes, "seconds": time.time() - t_dump}
     if rank == 0 and not line_first:
-        out["cpu_baseline"] = cpu_baseline(args.cpu_baseline_seconds, evals, args.mode, args.batch, args.config)
+        if args.cpu_baseline and world == 1:
+            out["cpu_baseline"] = cpu_baseline(args.cpu_baseline_seconds, evals, args.mode, args.batch, args.config)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

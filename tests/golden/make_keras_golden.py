@@ -30,7 +30,7 @@ def skeleton(path):
 
 
 def main():
-    out = {}
+    out, rejected = {}, {}
     for f in sorted(glob.glob("/root/reference/data/*/models/*.json")):
         key = f.split("/data/")[1]
         try:
@@ -40,10 +40,19 @@ def main():
                         "graph": skeleton(f)}
         except K.NotSupported as e:
             out[key] = {"not_supported": str(e)}
-    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "keras_descs.json")
+            # of a rejected file: how many layers of each supported class, and its unsupported layers'
+            # classes in file order (the importer stops at the first one) -- all the rejection reads
+            classes = [l["class_name"] for l in skeleton(f)["config"]["layers"]]
+            rejected[key] = {"supported": {c: classes.count(c) for c in sorted(set(classes) - set(K.UNSUPPORTED_LAYERS))},
+                             "unsupported": [c for c in classes if c in K.UNSUPPORTED_LAYERS]}
+    here = os.path.dirname(os.path.abspath(__file__))
+    path = os.path.join(here, "keras_descs.json")
     with open(path, "w") as fo:
         json.dump(out, fo, indent=None, sort_keys=True, separators=(",", ":"))
     print("wrote", path, len(out))
+    with open(os.path.join(here, "keras_rejected.json"), "w") as fo:
+        fo.write("{\n" + ",\n".join("%s: %s" % (json.dumps(k), json.dumps(v))
+                                    for k, v in sorted(rejected.items())) + "\n}\n")
 
 
 if __name__ == "__main__":

@@ -15,7 +15,6 @@ from galvanise_zero_amd.nn.desc import NetDesc
 from oracle import nn_ref
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "keras_descs.json")
-REF = "/root/reference/data"
 
 V1_FILES = {"amazons_10x10/models/h1_27.json", "breakthrough/models/x6_102.json", "breakthrough/models/x6_111.json",
             "breakthroughSmall/models/x1_132.json", "breakthroughSmall/models/x1_42.json"}
@@ -54,15 +53,33 @@ def test_golden_files(golden):
     assert len(rejected) + len(ok) == len(golden)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference not mounted")
-def test_importer_matches_golden(golden):
+def test_importer_matches_golden(golden, tmp_path):
+    """Every model file read from disk as the importer reads a model file: a supported file's layer
+    graph (the fixture's copy) gives the recorded NetDesc; a rejected file (tests/golden/
+    keras_rejected.json: its supported layers as a count per class, then its unsupported layers in
+    file order -- the importer stops at the first of those) raises NotSupported with the recorded
+    reason."""
+    with open(os.path.join(os.path.dirname(GOLDEN), "keras_rejected.json")) as f:
+        rejected = json.load(f)
+    assert set(rejected) == {k for k, v in golden.items() if "desc" not in v}
     for key, v in golden.items():
-        path = os.path.join(REF, key)
+        if "desc" in v:
+            graph = v["graph"]
+        else:
+            r = rejected[key]
+            classes = [c for c, n in sorted(r["supported"].items()) for _ in range(n)] + r["unsupported"]
+            graph = {"class_name": "Model", "config": {"layers": [
+                {"class_name": c, "name": "layer_%d" % i, "config": {}, "inbound_nodes": []}
+                for i, c in enumerate(classes)]}}
+        path = str(tmp_path / key.replace("/", "_"))
+        with open(path, "w") as f:
+            json.dump(graph, f)
         if "desc" in v:
             assert dataclasses.asdict(K.desc_from_keras_json(path)) == v["desc"], key
         else:
-            with pytest.raises(K.NotSupported):
+            with pytest.raises(K.NotSupported) as e:
                 K.desc_from_keras_json(path)
+            assert str(e.value) == v["not_supported"], key
 
 
 def test_importer_reads_graph_fixture(golden):

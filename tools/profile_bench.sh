@@ -21,5 +21,5 @@ timeout -k 10 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_W
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kv -o kv -- python3 $KV \
     > $OUT/kv_trace.log 2>&1 || { echo "kv trace pass failed"; exit 1; }
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- \
-    python3 $R/bench.py --no-cpu-baseline "$@" > $OUT/bench_trace.log 2>&1 || { echo "trace pass failed"; exit 1; }
+    python3 $R/bench.py --full --no-cpu-baseline "$@" > $OUT/bench_trace.log 2>&1 || { echo "trace pass failed"; exit 1; }
 echo PROFILE OK
