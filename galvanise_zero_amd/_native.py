@@ -64,24 +64,29 @@ class GzNetDesc(ctypes.Structure):
 
 GZ_PRECISION_BF16 = 1
 GZ_PRECISION_SPLIT = 3
+GZ_PRECISION_FP32 = 4
 # "bf16x3" (alias "split"): each fp32 operand as bf16 hi + lo, three MFMAs per product, ~16
 # significant bits per operand -- fp32-CLASS, not IEEE fp32: on the headline cfg2 batch its error
 # against the float64 oracle is ~35x an IEEE fp32 forward's (nn/tolerance.py).  "fp32" is the
 # pre-round-6 name of the same mode, kept as a deprecated alias.
+# "fp32-ieee": the reference's arithmetic -- every conv on the f32-input MFMA (f32 operands and
+# accumulation), layer by layer through a device scratch; about 16/3 of bf16x3's MFMA time.
 PRECISIONS = {"bf16": GZ_PRECISION_BF16, "bf16x3": GZ_PRECISION_SPLIT, "split": GZ_PRECISION_SPLIT,
-              "fp32": GZ_PRECISION_SPLIT}
+              "fp32": GZ_PRECISION_SPLIT, "fp32-ieee": GZ_PRECISION_FP32}
+_CANONICAL = {GZ_PRECISION_BF16: "bf16", GZ_PRECISION_SPLIT: "bf16x3", GZ_PRECISION_FP32: "fp32-ieee"}
 
 
 def canonical_precision(precision):
-    """The arithmetic mode's canonical name ("bf16" or "bf16x3"); "split" and the deprecated "fp32"
-    name bf16x3."""
+    """The arithmetic mode's canonical name ("bf16", "bf16x3" or "fp32-ieee"); "split" and the
+    deprecated "fp32" name bf16x3."""
     if precision not in PRECISIONS:
-        raise ValueError("precision %r: one of bf16, bf16x3 (alias split; fp32 is deprecated)" % (precision,))
+        raise ValueError("precision %r: one of bf16, bf16x3 (alias split), fp32-ieee (fp32 is a deprecated "
+                         "alias of bf16x3)" % (precision,))
     if precision == "fp32":
         import warnings
         warnings.warn('precision "fp32" selects the bf16x3 split mode (three bf16 MFMAs per product, '
                       'fp32-class, not IEEE fp32): use "bf16x3"', DeprecationWarning, stacklevel=3)
-    return "bf16" if PRECISIONS[precision] == GZ_PRECISION_BF16 else "bf16x3"
+    return _CANONICAL[PRECISIONS[precision]]
 
 
 _FP = ctypes.POINTER(ctypes.c_float)
@@ -129,6 +134,8 @@ def nn_lib():
         lib.gz_net_kernel_name.argtypes = [ctypes.c_void_p, ctypes.c_int]
         lib.gz_net_large_min_rows.restype = ctypes.c_int
         lib.gz_net_large_min_rows.argtypes = [ctypes.c_void_p]
+        lib.gz_net_wave_rows.restype = ctypes.c_int
+        lib.gz_net_wave_rows.argtypes = [ctypes.c_void_p]
         lib.gz_nn_last_error.restype = ctypes.c_char_p
         lib._gz_typed = True
     return lib
@@ -168,9 +175,12 @@ def _fptr(a):
 
 class HipNet(object):
     """Owner of a gz_net handle: the MI355X forward of one network on one device.
-    precision: "bf16" (bf16 operands) or "bf16x3" (alias "split"; hi/lo bf16 operands, three MFMAs
+    precision: "bf16" (bf16 operands), "bf16x3" (alias "split"; hi/lo bf16 operands, three MFMAs
     per product: fp32-class accuracy -- about 35x an IEEE fp32 forward's error on cfg2 -- not IEEE
-    fp32, include/gzero_nn.h GZ_PRECISION_SPLIT).  "fp32" is a deprecated alias of "bf16x3";
+    fp32, include/gzero_nn.h GZ_PRECISION_SPLIT) or "fp32-ieee" (GZ_PRECISION_FP32: IEEE fp32 like
+    the reference, on the f32-input MFMA, layer by layer through device memory -- every geometry up
+    to 19 x 19 / 256 filters, bit-identical rows whatever the batch; several times slower than
+    bf16x3: for match play, gating and numerics checks).  "fp32" is a deprecated alias of "bf16x3";
     self.precision holds the canonical name."""
 
     def __init__(self, desc, device=0, precision="bf16"):
@@ -253,7 +263,7 @@ class HipNet(object):
 
     def stamp_avg(self):
         out = (ctypes.c_double * 8)()
-        self.lib.gz_net_stamp_avg(self.handle, out)
+        self._check(self.lib.gz_net_stamp_avg(self.handle, out), "gz_net_stamp_avg")   # (fp32-ieee: none)
         return list(out)
 
     def flops_per_eval(self):
@@ -265,6 +275,10 @@ class HipNet(object):
 
     def large_min_rows(self):
         return self.lib.gz_net_large_min_rows(self.handle)
+
+    def wave_rows(self):
+        """Rows of one full wave of trunk workgroups (fp32-ieee: of its conv grid), gz_net_wave_rows."""
+        return self.lib.gz_net_wave_rows(self.handle)
 
     def heads_fused(self):
         """True when the large trunk variant runs the dense heads itself (no heads_kernel launch)."""

@@ -122,7 +122,7 @@ __host__ __device__ constexpr int align16(int x) { return (x + 15) & ~15; }
 
 // the dense policy / value heads (defined with heads_kernel below; the two-image trunk kernels call
 // it themselves)
-template <int BPW, int NT = 256>
+template <int BPW, int NT = 256, bool BLOCKED = false>
 __device__ __forceinline__ void dense_heads(const KParams& kp, const float* fk, float* lg, int board0, int nb);
 
 // The board geometry at run time (kernels are compiled per filter count and position-tile count):
@@ -1643,8 +1643,13 @@ trunk_kernel_v2(const KParams kp) {
 // the trunk kernel with BPW = its NB, or in heads_kernel with BPW = 4).  Every thread of the
 // workgroup (4 waves) must call it; boards board0 .. board0 + nb - 1 are written.
 constexpr int kGemmSoftmaxMax = 3072;   // policy rows the register softmax of gemm_heads takes (48 per lane)
+// BLOCKED (the exact-fp32 mode's heads_kernel_blocked only; every other caller keeps the serial
+// chain, bit for bit): each Dense sum runs in blocks of kDenseBlock terms, every block a chain from
+// zero added to the running total -- a 722-term policy Dense (19 x 19) otherwise carries a serial
+// fp32 chain's sqrt(K) rounding error, above that mode's own trunk error.  The k order stays fixed.
+constexpr int kDenseBlock = 64;
 
-template <int BPW, int NT>
+template <int BPW, int NT, bool BLOCKED = false>
 __device__ __forceinline__ void dense_heads_seq(const KParams& kp, const float* fk, float* lg, int board0, int nb) {
     static_assert(BPW >= 1 && BPW <= 4, "one softmax wave per board");
     const int NPOS = kp.npos;
@@ -1696,13 +1701,23 @@ __device__ __forceinline__ void dense_heads_seq(const KParams& kp, const float* 
         }
         for (int j = tid; j < P && !kp.gemm_heads; j += NT) {
             float a[BPW];
+            float tot[BPW];
 #pragma unroll
-            for (int b = 0; b < BPW; ++b) a[b] = 0.f;
+            for (int b = 0; b < BPW; ++b) a[b] = tot[b] = 0.f;
 #pragma unroll 32   // many weight loads in flight: the loop is L2-latency bound
             for (int k = 0; k < K; ++k) {
                 const float w = Wd[(size_t)k * ((P + 3) & ~3) + j];   // rows padded to P4
 #pragma unroll
                 for (int b = 0; b < BPW; ++b) a[b] += fr[k * BPW + b] * w;
+                if constexpr (BLOCKED)
+                    if ((k & (kDenseBlock - 1)) == kDenseBlock - 1) {
+#pragma unroll
+                        for (int b = 0; b < BPW; ++b) { tot[b] += a[b]; a[b] = 0.f; }
+                    }
+            }
+            if constexpr (BLOCKED) {
+#pragma unroll
+                for (int b = 0; b < BPW; ++b) a[b] = tot[b] + a[b];
             }
             const float bj = kp.pb[r][j];
 #pragma unroll
@@ -1737,13 +1752,23 @@ __device__ __forceinline__ void dense_heads_seq(const KParams& kp, const float* 
         const float* fv = fk + (size_t)2 * kp.R * NPOS * BPW;
         for (int j = tid; j < VH; j += NT) {
             float a[BPW];
+            float tot[BPW];
 #pragma unroll
-            for (int b = 0; b < BPW; ++b) a[b] = 0.f;
+            for (int b = 0; b < BPW; ++b) a[b] = tot[b] = 0.f;
 #pragma unroll 32   // many weight loads in flight: the loop is L2-latency bound
             for (int k = 0; k < VK; ++k) {
                 const float w = kp.vhw[(size_t)k * ((VH + 3) & ~3) + j];
 #pragma unroll
                 for (int b = 0; b < BPW; ++b) a[b] += fv[k * BPW + b] * w;
+                if constexpr (BLOCKED)
+                    if ((k & (kDenseBlock - 1)) == kDenseBlock - 1) {
+#pragma unroll
+                        for (int b = 0; b < BPW; ++b) { tot[b] += a[b]; a[b] = 0.f; }
+                    }
+            }
+            if constexpr (BLOCKED) {
+#pragma unroll
+                for (int b = 0; b < BPW; ++b) a[b] = tot[b] + a[b];
             }
             const float bj = kp.vhb[j];
 #pragma unroll
@@ -1788,11 +1813,11 @@ __device__ __forceinline__ void dense_heads_seq(const KParams& kp, const float* 
 // a barrier and a softmax between them (the weight loads are L2-latency bound); (B) one wave per
 // (role, board) softmax and per board's value output.  lg: per board a row of kp.lgrow floats,
 // [P4_0 | P4_1 | .. | VH4] (the policy sections absent with gemm_heads).
-template <int BPW, int NT>
+template <int BPW, int NT, bool BLOCKED>
 __device__ __forceinline__ void dense_heads(const KParams& kp, const float* fk, float* lg, int board0, int nb) {
     static_assert(BPW >= 1 && BPW <= 4, "one softmax wave per board");
     if (kp.heads_seq || (kp.gemm_heads && kp.maxP > kGemmSoftmaxMax)) {
-        dense_heads_seq<BPW, NT>(kp, fk, lg, board0, nb);
+        dense_heads_seq<BPW, NT, BLOCKED>(kp, fk, lg, board0, nb);
         return;
     }
     const int NPOS = kp.npos, R = kp.R, LG = kp.lgrow;
@@ -1831,8 +1856,12 @@ __device__ __forceinline__ void dense_heads(const KParams& kp, const float* fk, 
             off = voff;
         }
         float a[BPW][4];
+        float tot[BPW][4];
 #pragma unroll
-        for (int b = 0; b < BPW; ++b) a[b][0] = a[b][1] = a[b][2] = a[b][3] = 0.f;
+        for (int b = 0; b < BPW; ++b) {
+            a[b][0] = a[b][1] = a[b][2] = a[b][3] = 0.f;
+            tot[b][0] = tot[b][1] = tot[b][2] = tot[b][3] = 0.f;
+        }
         const float4* w4 = (const float4*)W + q;
         const int rs = N4 >> 2;
 #pragma unroll 16   // many weight loads in flight: the loop is L2-latency bound
@@ -1846,6 +1875,19 @@ __device__ __forceinline__ void dense_heads(const KParams& kp, const float* fk, 
                 a[b][2] += x * w.z;
                 a[b][3] += x * w.w;
             }
+            if constexpr (BLOCKED)
+                if ((k & (kDenseBlock - 1)) == kDenseBlock - 1) {
+#pragma unroll
+                    for (int b = 0; b < BPW; ++b)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) { tot[b][i] += a[b][i]; a[b][i] = 0.f; }
+                }
+        }
+        if constexpr (BLOCKED) {
+#pragma unroll
+            for (int b = 0; b < BPW; ++b)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) a[b][i] = tot[b][i] + a[b][i];
         }
         if (u < pgroups) {
 #pragma unroll
@@ -2026,7 +2068,8 @@ __global__ void __launch_bounds__(256) policy_gemm_kernel(const KParams kp) {
     }
 }
 
-__global__ void __launch_bounds__(256) heads_kernel(const KParams kp) {
+template <bool BLOCKED>
+__device__ __forceinline__ void heads_body(const KParams& kp) {
     constexpr int BPW = kHeadBoards;
     extern __shared__ __attribute__((aligned(16))) float hs[];
     const int FS = kp.FS;
@@ -2052,8 +2095,12 @@ __global__ void __launch_bounds__(256) heads_kernel(const KParams kp) {
         }
     }
     __syncthreads();
-    dense_heads<BPW>(kp, fk, lg, board0, nb);
+    dense_heads<BPW, 256, BLOCKED>(kp, fk, lg, board0, nb);
 }
+
+__global__ void __launch_bounds__(256) heads_kernel(const KParams kp) { heads_body<false>(kp); }
+// the exact-fp32 mode's heads: the same kernel with blocked Dense sums (kDenseBlock)
+__global__ void __launch_bounds__(256) heads_kernel_blocked(const KParams kp) { heads_body<true>(kp); }
 
 #endif
 

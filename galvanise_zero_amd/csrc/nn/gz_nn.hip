@@ -6,6 +6,7 @@
 #define GZNN_DEFINE_HEADS_KERNEL
 #include "forward_kernel.h"
 #include "trunk_variants.h"
+#include "fp32_forward.h"
 #include "../../../include/gzero_nn.h"
 
 #include <hip/hip_runtime.h>
@@ -78,6 +79,13 @@ struct gz_net {
     int stamp_cap = 0;
     bool stamps_on = false;
     double stamp_avg[8] = {0};
+    // GZ_PRECISION_FP32 (fp32_forward.h): fp32 conv images, the layer-wise trunk's scratch per stream
+    bool fp32 = false;
+    int cp = 0;                    // input planes padded to 16
+    int chunk_rows = 1;            // rows per sequential chunk of a launch (GZ_FP32_CHUNK_ROWS overrides)
+    const float* w0f = nullptr;
+    const float* wresf = nullptr;
+    std::map<hipStream_t, std::pair<char*, int>> fscr;   // scratch and the rows it holds
 };
 
 extern "C" const char* gz_nn_last_error(void) { return g_err.c_str(); }
@@ -174,7 +182,8 @@ extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
         return nullptr;
     }
     const int precision = d.precision == 0 ? GZ_PRECISION_BF16 : d.precision;
-    if (precision != GZ_PRECISION_BF16 && precision != GZ_PRECISION_SPLIT) { fail("unknown precision"); return nullptr; }
+    const bool fp32 = precision == GZ_PRECISION_FP32;
+    if (precision != GZ_PRECISION_BF16 && precision != GZ_PRECISION_SPLIT && !fp32) { fail("unknown precision"); return nullptr; }
     int vs = kSmallVariant, vl = kLargeVariant, min_large = kLargeMinRows;
     if (const char* e = getenv("GZ_KERNEL_VARIANT")) {   // experiments: one fixed variant
         vs = vl = atoi(e);
@@ -184,11 +193,22 @@ extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
     // are kernel arguments (H = input_columns, W = input_rows: bases.py:104-121)
     const int npos_ = d.input_columns * d.input_rows;
     const int pt = kernel_tiles((npos_ + 15) / 16);
-    const int fpad = kernel_filters(d.cnn_filter_size, (npos_ + 15) / 16);
+    const int fpad = fp32 ? gzfp32::padded_filters(d.cnn_filter_size) : kernel_filters(d.cnn_filter_size, (npos_ + 15) / 16);
     if (d.input_rows > 32 || npos_ >= 1024) { fail("board too large"); return nullptr; }
     const bool v2 = d.resnet_v2 != 0;
-    KernelChoice kc = select_kernel(fpad, pt, vs, precision, v2);
-    KernelChoice kl = select_kernel(fpad, pt, vl, precision, v2);
+    if (fp32) {
+        // the layer-wise fp32 path has no LDS-image limit: any board up to 19 x 19, F <= 256, v1 or v2
+        if (d.input_columns < 1 || d.input_rows < 1 || d.input_columns > gzfp32::kMaxBoardSide ||
+            d.input_rows > gzfp32::kMaxBoardSide || fpad == 0 || d.input_channels < 1) {
+            fail("unsupported network geometry F=" + std::to_string(d.cnn_filter_size) + " H=" +
+                 std::to_string(d.input_columns) + " W=" + std::to_string(d.input_rows) +
+                 " (fp32-ieee: boards up to 19 x 19, F <= 256)");
+            return nullptr;
+        }
+        min_large = 1 << 30;   // one conv kernel for every launch size
+    }
+    KernelChoice kc = fp32 ? KernelChoice{} : select_kernel(fpad, pt, vs, precision, v2);
+    KernelChoice kl = fp32 ? KernelChoice{} : select_kernel(fpad, pt, vl, precision, v2);
     if (!kl.fn && vl == kLargeVariant) kl = select_kernel(fpad, pt, kLargeFallback, precision, v2);
     // wave-group kernels: each group's staging / heads scratch must fit its own image
     auto wg_fits = [&](const KernelChoice& c) {
@@ -215,7 +235,7 @@ extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
         kl = kc;
         min_large = 1 << 30;
     }
-    if (!kc.fn || !kl.fn) {
+    if (!fp32 && (!kc.fn || !kl.fn)) {
         fail("unsupported network geometry F=" + std::to_string(d.cnn_filter_size) + " H=" +
              std::to_string(d.input_columns) + " W=" + std::to_string(d.input_rows) +
              (precision == GZ_PRECISION_SPLIT ? " (split precision)" : "") + (v2 ? " (v2 nets: F <= 128)" : ""));
@@ -227,6 +247,13 @@ extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
     net->large_min_rows = min_large;
     net->p2 = precision == GZ_PRECISION_SPLIT ? 2 : 1;
     net->fpad = fpad;
+    net->fp32 = fp32;
+    net->cp = gzfp32::pad16(d.input_channels);
+    if (fp32) {
+        net->chunk_rows = gzfp32::chunk_rows_for(npos_, net->cp, fpad);
+        if (const char* e = getenv("GZ_FP32_CHUNK_ROWS"))   // tests: chunking without a large launch
+            net->chunk_rows = std::max(1, std::min(atoi(e), net->chunk_rows));
+    }
     const int k0 = initial_kernel(d);
     net->K0 = ((k0 * k0 * d.input_channels + 31) / 32) * 32;
     net->nweights = spec_count(d);
@@ -264,6 +291,11 @@ extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
     for (int pass = 0; pass < 2; ++pass) {
         net->small = trunk(kc);
         net->large = trunk(kl);
+        if (fp32) {   // no trunk kernel: fp32_forward.hip's launches, then heads_kernel
+            gz_net::Trunk t;
+            t.name = gzfp32::conv_kernel_name(fpad);
+            net->small = net->large = t;
+        }
         net->heads_smem = heads_lds_bytes(FS, lgrow);
         if (pass == 1 || (net->small.smem <= 160 * 1024 && net->large.smem <= 160 * 1024 && net->heads_smem <= 160 * 1024))
             break;
@@ -274,7 +306,8 @@ extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
     // layers run as one MFMA GEMM per launch (policy_gemm_kernel) instead of heads_kernel's
     // per-4-board fp32 loop (amazons P = 3041: 12 % of the forward).  Every launch of such a net
     // takes this path, so results stay batch-invariant.
-    net->gemm_heads = !net->small.fused_heads && !net->large.fused_heads && maxP >= 512 &&
+    // (fp32-ieee: the policy Dense stays fp32 on the VALU)
+    net->gemm_heads = !fp32 && !net->small.fused_heads && !net->large.fused_heads && maxP >= 512 &&
                       getenv("GZ_NO_GEMM_HEADS") == nullptr;
     KParams& kp = net->kp;
     kp.C = d.input_channels;
@@ -328,8 +361,8 @@ extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
         }
     }
     if (net->heads_smem > 64 * 1024 &&
-        hipFuncSetAttribute((const void*)&heads_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, net->heads_smem) !=
-            hipSuccess) {
+        hipFuncSetAttribute(fp32 ? (const void*)&heads_kernel_blocked : (const void*)&heads_kernel,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, net->heads_smem) != hipSuccess) {
         fail("cannot raise dynamic LDS limit (heads)");
         delete net;
         return nullptr;
@@ -346,6 +379,7 @@ extern "C" void gz_net_destroy(gz_net* net) {
     for (auto& f : net->feat) (void)hipFree(f.second.first);
     for (auto& f : net->resid) (void)hipFree(f.second.first);
     for (auto& f : net->glog) (void)hipFree(f.second.first);
+    for (auto& f : net->fscr) (void)hipFree(f.second.first);
     if (net->ev0) (void)hipEventDestroy(net->ev0);
     if (net->ev1) (void)hipEventDestroy(net->ev1);
     if (net->stream) (void)hipStreamDestroy(net->stream);
@@ -395,7 +429,10 @@ ImageLayout image_layout(const gz_net* net) {
     const int HW = d.input_columns * d.input_rows, HC = 2 * R + 1, NL = cal_layers(d);
     const int VH = d.value_hidden_size, VK = value_features(d);
     ImageLayout I;
-    I.n_w0 = (size_t)net->K0 * FP;
+    // (fp32-ieee: fp32 conv images in fp32_forward.h's wfrag_index order in place of the bf16 ones)
+    const size_t wb = net->fp32 ? 4 : 2;
+    const int k0 = initial_kernel(d);
+    I.n_w0 = net->fp32 ? gzfp32::conv_image_floats(k0 * k0, net->cp, FP) : (size_t)net->K0 * FP;
     I.n_wres = (size_t)P2 * 2 * B * 9 * FP * FP;
     I.n_wh = (size_t)HC * FP;
     I.n_wcl = (size_t)std::max(NL, 1) * FP;
@@ -405,10 +442,10 @@ ImageLayout image_layout(const gz_net* net) {
     I.n_sew1 = S ? (size_t)B * FP * S : 1;
     I.n_sew2 = S ? (size_t)B * S * FP : 1;
     Layout L;
-    I.w0 = L.alloc(I.n_w0 * 2);
+    I.w0 = L.alloc(I.n_w0 * wb);
     I.w0lo = L.alloc((P2 == 2 ? I.n_w0 : 1) * 2);
     I.b0 = L.alloc((size_t)FP * 4);
-    I.wres = L.alloc(I.n_wres * 2);
+    I.wres = L.alloc(I.n_wres * wb);
     I.bres = L.alloc((size_t)2 * B * FP * 4);
     I.wh = L.alloc(I.n_wh * 4);
     I.bh = L.alloc((size_t)HC * 4);
@@ -449,6 +486,8 @@ int install_image(gz_net* net, char* m, const ImageLayout& I) {
     kp.w0lo = (const __bf16*)(m + I.w0lo);
     kp.b0 = (const float*)(m + I.b0);
     kp.wres = (const __bf16*)(m + I.wres);
+    net->w0f = (const float*)(m + I.w0);
+    net->wresf = (const float*)(m + I.wres);
     kp.bres = (const float*)(m + I.bres);
     kp.wh = (const float*)(m + I.wh);
     kp.bh = (const float*)(m + I.bh);
@@ -493,9 +532,13 @@ extern "C" int gz_net_set_weights(gz_net* net, const float* blob, size_t count) 
 
     // host images
     const int P2 = net->p2;
-    std::vector<uint16_t> w0((size_t)K0 * FP, 0), w0lo(P2 == 2 ? (size_t)K0 * FP : 0, 0);
+    const bool fp32 = net->fp32;   // fp32 conv images (w0f, wresf) instead of the bf16 ones
+    const int k0i = initial_kernel(d);
+    std::vector<uint16_t> w0(fp32 ? 0 : (size_t)K0 * FP, 0), w0lo(P2 == 2 ? (size_t)K0 * FP : 0, 0);
     std::vector<float> b0(FP, 0.f);
-    std::vector<uint16_t> wres((size_t)P2 * 2 * B * 9 * FP * FP, 0);
+    std::vector<uint16_t> wres(fp32 ? 0 : (size_t)P2 * 2 * B * 9 * FP * FP, 0);
+    std::vector<float> w0f(fp32 ? gzfp32::conv_image_floats(k0i * k0i, net->cp, FP) : 0, 0.f);
+    std::vector<float> wresf(fp32 ? (size_t)2 * B * gzfp32::conv_image_floats(9, FP, FP) : 0, 0.f);
     // split precision: x = hi + lo, hi = bf16(x), lo = bf16(x - hi)
     auto lo_of = [](float v) {
         const uint16_t h = f2bf(v);
@@ -536,8 +579,10 @@ extern "C" int gz_net_set_weights(gz_net* net, const float* blob, size_t count) 
             bb.assign(F, 0.f);
             if (cb) for (int i = 0; i < F; ++i) bb[i] = cb[i];
         }
+        if (fp32) gzfp32::pack_conv_host(w0f.data(), w, s.data(), T0, C, net->cp, F, FP);
         for (int co = 0; co < F; ++co) {
             b0[co] = bb[co];
+            if (fp32) continue;   // (packed above)
             for (int k = 0; k < T0 * C; ++k) {
                 const int tap = k / C, c = k % C;
                 const float v = w[((size_t)tap * C + c) * F + co] * s[co];
@@ -548,6 +593,11 @@ extern "C" int gz_net_set_weights(gz_net* net, const float* blob, size_t count) 
     }
     // trunk conv `conv` [3][3][F][F] * scale[co] -> wres_index order, bias[co] -> bres
     auto pack_conv = [&](int conv, const float* w, const std::vector<float>& scale, const std::vector<float>& bias) {
+        if (fp32) {
+            gzfp32::pack_conv_host(wresf.data() + (size_t)conv * gzfp32::conv_image_floats(9, FP, FP), w, scale.data(), 9, F, FP, F, FP);
+            for (int co = 0; co < F; ++co) bres[(size_t)conv * FP + co] = bias[co];
+            return;
+        }
         uint16_t* dst = wres.data() + (size_t)P2 * conv * 9 * FP * FP;
         for (int co = 0; co < F; ++co) {
             bres[(size_t)conv * FP + co] = bias[co];
@@ -672,8 +722,12 @@ extern "C" int gz_net_set_weights(gz_net* net, const float* blob, size_t count) 
     }
 
     std::vector<char> img(I.total, 0);
-    auto put = [&](size_t off, const void* src, size_t bytes) { std::memcpy(img.data() + off, src, bytes); };
+    auto put = [&](size_t off, const void* src, size_t bytes) { if (bytes) std::memcpy(img.data() + off, src, bytes); };
     put(I.w0, w0.data(), w0.size() * 2);
+    if (fp32) {
+        put(I.w0, w0f.data(), w0f.size() * 4);
+        put(I.wres, wresf.data(), wresf.size() * 4);
+    }
     if (P2 == 2) put(I.w0lo, w0lo.data(), w0lo.size() * 2);
     put(I.b0, b0.data(), b0.size() * 4);
     put(I.wres, wres.data(), wres.size() * 2);
@@ -873,6 +927,18 @@ __global__ void pack_w0_kernel(const float* w, const float* scale, const float* 
     }
 }
 
+// fp32-ieee: one conv [taps][cin][F] * scale[co] -> fp32_forward.h's wfrag_index order (+ its bias
+// row): pack_conv_host's values, the product rounded once as on the host
+__global__ void pack_conv_f32_kernel(const float* w, const float* scale, const float* bias, float* dst, float* brow,
+                                     int taps, int cin, int cinp, int F, int FP) {
+    const size_t n = (size_t)taps * cin * F;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int co = (int)(i % F), ci = (int)((i / F) % cin), tap = (int)(i / ((size_t)F * cin));
+        dst[gzfp32::wfrag_index(tap, co, ci, cinp, FP)] = f_mul(w[i], scale[co]);
+        if (tap == 0 && ci == 0) brow[co] = bias[co];
+    }
+}
+
 // dst[i ds] = src[i ss] (mode 0), * sc[i] (1), * sc[0] (2)
 struct VecJob {
     const float* src;
@@ -992,13 +1058,23 @@ extern "C" int gz_net_set_weights_device(gz_net* net, const float* d_blob, size_
     if (!vj.empty() && (e = hipMemcpyAsync(vj_d, vj.data(), vj_bytes, hipMemcpyHostToDevice, st)) != hipSuccess)
         return bail("jobs", e);
     hipLaunchKernelGGL(bn_fold_kernel, dim3((unsigned)bj.size()), dim3(256), 0, st, bj_d, fold);
-    {   // initial conv
+    if (net->fp32) {   // fp32 conv images
+        const int T0 = initial_kernel(d) * initial_kernel(d), C = d.input_channels;
+        const size_t n0 = (size_t)T0 * C * F, nc = (size_t)9 * F * F;
+        hipLaunchKernelGGL(pack_conv_f32_kernel, dim3((unsigned)std::min<size_t>((n0 + 255) / 256, 4096)), dim3(256), 0, st,
+                           P.w0, sc_of(P.bn0), bi_of(P.bn0), (float*)(mc + I.w0), (float*)(mc + I.b0), T0, C, net->cp, F, FP);
+        for (int c = 0; c < 2 * B; ++c)
+            hipLaunchKernelGGL(pack_conv_f32_kernel, dim3((unsigned)std::min<size_t>((nc + 255) / 256, 4096)), dim3(256), 0, st,
+                               P.wconv[c], sc_of(P.bnconv[c]), bi_of(P.bnconv[c]),
+                               (float*)(mc + I.wres) + (size_t)c * gzfp32::conv_image_floats(9, FP, FP),
+                               (float*)(mc + I.bres) + (size_t)c * FP, 9, F, FP, F, FP);
+    } else {   // initial conv
         const int KF = initial_kernel(d) * initial_kernel(d) * d.input_channels * F;
         hipLaunchKernelGGL(pack_w0_kernel, dim3((KF + 255) / 256), dim3(256), 0, st, P.w0, sc_of(P.bn0), bi_of(P.bn0),
                            (uint16_t*)(mc + I.w0), P2 == 2 ? (uint16_t*)(mc + I.w0lo) : (uint16_t*)nullptr,
                            (float*)(mc + I.b0), KF, F, FP);
     }
-    for (int c = 0; c < 2 * B; ++c) {
+    for (int c = 0; c < (net->fp32 ? 0 : 2 * B); ++c) {
         const size_t n = (size_t)9 * F * F;
         hipLaunchKernelGGL(pack_conv_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, st,
                            P.wconv[c], sc_of(P.bnconv[c]), bi_of(P.bnconv[c]),
@@ -1111,6 +1187,40 @@ static int launch_segments(gz_net* net, hipStream_t stream, const gz_segment* se
             }
             kp.glog = g.first;
         }
+    }
+    if (net->fp32) {   // the layer-wise fp32 trunk (fp32_forward.hip), then the heads kernel (blocked Dense sums)
+        gzfp32::Forward f;
+        f.w0 = net->w0f;
+        f.wres = net->wresf;
+        f.CP = net->cp;
+        f.FP = net->fpad;
+        f.chunk_rows = net->chunk_rows;
+        {   // this stream's activation scratch (grown with a device sync: rare, sizes only increase)
+            std::lock_guard<std::mutex> lk(net->feat_mu);
+            auto& s = net->fscr[stream];
+            const int need = std::min(n, net->chunk_rows);
+            if (s.second < need) {
+                if (s.first) {
+                    HIPCHK(hipDeviceSynchronize());
+                    HIPCHK(hipFree(s.first));
+                    s.first = nullptr;
+                    s.second = 0;
+                }
+                const int cap = std::max(need, std::min(net->chunk_rows, 64));
+                HIPCHK(hipMalloc((void**)&s.first, gzfp32::scratch_layout(cap, kp.npos, f.CP, f.FP).total));
+                s.second = cap;
+            }
+            f.scratch = s.first;
+            f.scratch_rows = s.second;
+            f.scratch_bytes = gzfp32::scratch_layout(s.second, kp.npos, f.CP, f.FP).total;
+        }
+        if (f.scratch_bytes > gzfp32::kScratchMax) return fail("internal: fp32 scratch over its limit");
+        if (const char* e = gzfp32::forward(kp, f, stream)) return fail(e);
+        if (mid) HIPCHK(hipEventRecord(mid, stream));
+        void* hargs[] = {&kp};
+        HIPCHK(hipLaunchKernel((const void*)&heads_kernel_blocked, dim3((n + kHeadBoards - 1) / kHeadBoards), dim3(256), hargs,
+                               net->heads_smem, stream));
+        return 0;
     }
     const gz_net::Trunk& t = n >= net->large_min_rows ? net->large : net->small;
     kp.resid = nullptr;
@@ -1232,6 +1342,7 @@ extern "C" int gz_net_forward(gz_net* net, const float* planes, int n, float* co
 }
 
 extern "C" int gz_net_stamp_avg(const gz_net* net, double* out8) {
+    if (net && net->fp32) return fail("no kernel stamps in fp32-ieee mode (the trunk is many launches)");
     for (int i = 0; i < 8; ++i) out8[i] = net->stamp_avg[i];
     return 0;
 }
@@ -1254,5 +1365,9 @@ extern "C" const char* gz_net_kernel_name(const gz_net* net, int large) {
 
 extern "C" int gz_net_wave_rows(const gz_net* net) {
     if (!net) return 0;
+    if (net->fp32) {   // rows whose conv grid is one workgroup per CU
+        const int gy = net->fpad / (32 * gzfp32::wave_co_tiles(net->fpad));
+        return std::max(1, (kCUs / gy) * gzfp32::kTileCols / net->kp.npos);
+    }
     return (net->large_min_rows < (1 << 30) ? net->large.nb : net->small.nb) * kCUs;
 }

@@ -27,6 +27,16 @@ accumulation and an fp32 residual stream.  It is fp32-CLASS, not fp32: on the he
 float64 oracle is 1.5-2.0e-4, about 35x the 5.7e-6 of an IEEE fp32 forward of the same net (torch
 fp32 on the CPU), and 300x below bf16's 5.9e-2.
 
+The three modes: "bf16" (bf16 operands; 1e-2-class errors on deep nets; fastest), "bf16x3" (above; the
+bench's and self-play's mode) and "fp32-ieee" (GZ_PRECISION_FP32: every conv on the f32-input MFMA,
+fp32 activations, blocked fp32 sums -- the reference's arithmetic).  fp32-ieee's error against the
+float64 oracle is a true fp32 forward's: 0.2-1.6x torch-CPU fp32's on every v1 case of
+tests/test_nn_fp32_gpu.py, whose bound is 4 x max(torch fp32's error, 1e-6) (cfg2 on the bench's
+weights: 2.1e-6 at 37 rows, 4.7e-6 at 256 rows against bf16x3's 9.7e-5); v2 nets' relative logit
+error is 1.9-3.7e-7 against bf16x3's 2.7-5.1e-6.  It costs 4.2x a bf16x3 forward: use
+it for match play, gating games and for separating a wrong net from a saturated softmax moved by
+the split arithmetic; the constants below are bf16x3's.
+
 The north-star tolerance per config, then:
   cfg2, cfg3   the probability bounds below (max / mean / KL), on the bench's weights
   cfg4, cfg5   the relative logits bound below on the bench's (saturating) weights, and in probability

@@ -50,6 +50,13 @@ typedef struct gz_net_desc {
      *   fp32 in both modes; the policy Dense is fp32 except for single-image nets with a policy of
      *   >= 512 moves (amazons), whose policy Dense of the whole launch runs as one bf16x3 split MFMA
      *   GEMM in both modes (policy_gemm_kernel; GZ_NO_GEMM_HEADS=1 keeps it fp32 on the VALU).
+     *   GZ_PRECISION_FP32 (4): IEEE fp32, the reference's arithmetic -- every conv on the f32-input
+     *   MFMA (v_mfma_f32_16x16x4_f32: f32 operands, f32 accumulation, a k-ordered fmaf chain), BN
+     *   folded in fp32, fp32 activations.  The trunk runs layer by layer through a device scratch
+     *   (no LDS-image limit: every board up to 19 x 19 with F <= 256, v1 and v2), large launches in
+     *   sequential row chunks; the heads kernel follows and the policy Dense is always fp32.  About
+     *   16/3 of the split mode's MFMA time: for match play, gating and numerics checks, not for
+     *   self-play throughput.  Every row's outputs are bit-identical whatever the launch.
      *   Stated error per config: galvanise_zero_amd/nn/tolerance.py. */
     int precision;
     /* v2 (pre-activation) trunk, model.py:78-151 (the reference's features=True templates and its
@@ -67,6 +74,7 @@ typedef struct gz_net_desc {
 
 #define GZ_PRECISION_BF16 1
 #define GZ_PRECISION_SPLIT 3
+#define GZ_PRECISION_FP32 4
 
 typedef struct gz_net gz_net;
 
@@ -138,15 +146,19 @@ int gz_net_set_output_logits(gz_net* net, int on);
 float gz_net_last_kernel_ms(const gz_net* net);
 
 /* Launches of at least this many rows run the two-boards-per-workgroup trunk variant, smaller ones
- * the one-board variant (both compute every row identically). */
+ * the one-board variant (both compute every row identically).  GZ_PRECISION_FP32 has one conv
+ * kernel for every launch size: 1 << 30, as for geometries with a single variant. */
 int gz_net_large_min_rows(const gz_net* net);
 
 /* The trunk kernel of launches below (large = 0) / from (large = 1) gz_net_large_min_rows rows, as
- * rocprofv3 names it (diagnostics: the bench reports its roofline per kernel). */
+ * rocprofv3 names it (diagnostics: the bench reports its roofline per kernel).  GZ_PRECISION_FP32:
+ * the conv kernel, for both. */
 const char* gz_net_kernel_name(const gz_net* net, int large);
 
 /* Rows one full wave of workgroups of the large variant covers (boards per workgroup x 256 CUs,
- * one trunk workgroup per CU): the native runner launches multiples of it beyond one wave. */
+ * one trunk workgroup per CU): the native runner launches multiples of it beyond one wave.
+ * GZ_PRECISION_FP32: the rows whose conv grid (128 board positions x 64 / 128 filters per
+ * workgroup) is one workgroup per CU. */
 int gz_net_wave_rows(const gz_net* net);
 
 /* Algorithmic FLOPs of one leaf evaluation (2 FLOP/MAC). */
@@ -161,7 +173,7 @@ const char* gz_nn_last_error(void);
 /* Diagnostics: with GZ_KERNEL_STAMPS set in the environment, gz_net_forward records per-workgroup
  * s_memtime stamps at phase boundaries; out8[0] = workgroups averaged, out8[1..4] = their mean
  * cycles of (input + initial conv, residual trunk, head 1x1 convs + features, fused dense heads)
- * in the last call. */
+ * in the last call.  GZ_PRECISION_FP32 (many launches per forward) has no stamps: an error. */
 int gz_net_stamp_avg(const gz_net* net, double* out8);
 
 /* ---- native self-play driver (runner.hip) ----------------------------------------------------
