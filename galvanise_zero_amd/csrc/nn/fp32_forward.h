@@ -2,7 +2,7 @@
 // through HBM on the f32-input MFMA (v_mfma_f32_16x16x4_f32: f32 operands, f32 accumulation -- a
 // k-ordered fmaf chain), fp32 activations in a per-stream device scratch, the existing fp32
 // heads_kernel on the head features.  fp32_forward.hip holds the kernels; this header holds
-//   * the index arithmetic the conv kernel, the host / device weight packing and the CPU check
+//   * the index arithmetic the conv kernel, the weight packing (weight_image.h) and the CPU check
 //     (tests/fp32_host_check.cpp) share -- plain C++, usable without a HIP compiler;
 //   * the launch interface gz_nn.hip calls (HIP compilers only).
 //
@@ -72,17 +72,6 @@ GZF_HD inline size_t wfrag_index(int tap, int co, int ci, int cinp, int FP) {
 }
 GZF_HD inline size_t conv_image_floats(int taps, int cinp, int FP) { return (size_t)taps * cinp * FP; }
 
-// One conv's kernel (Keras HWIO [taps][cin][F]) times scale[co] into the zeroed image dst
-// (conv_image_floats(taps, cinp, FP) floats; cinp >= cin input channels of the activations it
-// multiplies): the host packing of gz_net_set_weights.  The product is one fp32 multiply, as the
-// device packing's.
-inline void pack_conv_host(float* dst, const float* w, const float* scale, int taps, int cin, int cinp, int F, int FP) {
-    for (int tap = 0; tap < taps; ++tap)
-        for (int ci = 0; ci < cin; ++ci)
-            for (int co = 0; co < F; ++co)
-                dst[wfrag_index(tap, co, ci, cinp, FP)] = w[((size_t)tap * cin + ci) * F + co] * scale[co];
-}
-
 // ---- device scratch and row chunks -------------------------------------------------------------
 // Per row: the gathered input [npos][CP], the ping / pong images and the residual stream
 // [npos][FP] each, the squeeze-excite gates [FP]; every buffer starts 256-byte aligned.
@@ -120,6 +109,12 @@ GZF_HD inline void chunk_bounds(int n, int chunk_rows, int i, int* first, int* c
 GZF_HD inline int chunk_count(int n, int chunk_rows) { return (n + chunk_rows - 1) / chunk_rows; }
 
 }  // namespace gzfp32
+
+// gzfp32::pack_conv_host(dst, w, scale, taps, cin, cinp, F, FP) -- one conv's kernel times scale[co]
+// into the zeroed image dst, in wfrag_index order -- comes with the weight packing, whose fp32 conv
+// element it loops over.  (weight_image.h includes this header for the index arithmetic above;
+// whichever of the two is included first, both are complete after it.)
+#include "weight_image.h"
 
 #if defined(__HIPCC__)
 #include "forward_kernel.h"

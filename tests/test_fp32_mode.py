@@ -23,19 +23,45 @@ def test_host_check_sanitised(tmp_path):
     row stride, weight-fragment index, chunk bounds) and host packing routine run a conv with the
     kernel's tiling on 6 x 6 .. 19 x 19 boards, F 64 / 80 -> 128 / 256, 3 / 15 / 24 planes, against
     a naive 'same' conv, every index asserted in bounds -- built with -fsanitize=address,undefined."""
-    cxx = shutil.which("g++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler"
-    exe = str(tmp_path / "fp32_host_check")
-    # (the sanitizer runtimes linked into the program itself)
-    static = ["-static-libasan", "-static-libubsan"] if os.path.basename(cxx) == "g++" else ["-static-libsan"]
-    subprocess.run([cxx, "-std=c++17", "-O2", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] + static +
-                   ["-o", exe, os.path.join(ROOT, "tests", "fp32_host_check.cpp")], check=True)
-    p = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True)
-    print(p.stdout)
+    p = _run_sanitised(tmp_path, "fp32_host_check")
     assert p.returncode == 0, p.stdout[-4000:]
     assert len(re.findall(r"max rel err", p.stdout)) >= 40
     for side in (6, 8, 13, 19):
         assert "H=%d W=%d" % (side, side) in p.stdout
+
+
+def _run_sanitised(tmp_path, name, args=()):
+    """Builds tests/<name>.cpp with -fsanitize=address,undefined and runs it."""
+    cxx = shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    exe = str(tmp_path / name)
+    # (the sanitizer runtimes linked into the program itself)
+    static = ["-static-libasan", "-static-libubsan"] if os.path.basename(cxx) == "g++" else ["-static-libsan"]
+    subprocess.run([cxx, "-std=c++17", "-O2", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] + static +
+                   ["-o", exe, os.path.join(ROOT, "tests", name + ".cpp")], check=True)
+    p = subprocess.run([exe] + [str(a) for a in args], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True)
+    print(p.stdout)
+    return p
+
+
+def test_weight_image_host_check_sanitised(tmp_path):
+    """tests/weight_image_host_check.cpp: csrc/nn/weight_image.h's job list packed on the CPU for
+    four small nets -- (a) legacy v1 on a 5 x 4 board, F 40 -> 64, (b) v2 with F 96 -> 128, a bare
+    3 x 3 initial conv, squeeze-excite and the pooling value head, (c) v2 concat_all_layers, (d) the
+    GEMM heads' fragments of a 530-move policy on 2 HW = 50 inputs -- each as bf16, bf16x3 and fp32,
+    into heap buffers of exactly the image's size.  The blob plan must consume the float count
+    weight_spec gives for the same desc (passed in); the program asserts the rest."""
+    from galvanise_zero_amd.nn.desc import blob_size
+    descs = [
+        NetDesc(3, 5, 4, 40, 1, [7, 9], value_hidden_size=6, conv_bias=True, value_bn=True, value_sigmoid=True),
+        NetDesc(5, 6, 6, 96, 2, [37, 37], value_hidden_size=6, resnet_v2=True, initial_kernel_size=3, initial_bn=False,
+                se_units=4, global_pooling_value=True, value_bn=True),
+        NetDesc(3, 4, 3, 40, 2, [13], value_hidden_size=6, resnet_v2=True, concat_all_layers=True),
+        NetDesc(3, 5, 5, 40, 1, [530], value_hidden_size=6),
+    ]
+    p = _run_sanitised(tmp_path, "weight_image_host_check", [blob_size(d) for d in descs])
+    assert p.returncode == 0, p.stdout[-4000:]
+    assert len(re.findall(r"^case [abcd] (p2=1|p2=2|fp32): ", p.stdout, re.M)) == 12
 
 
 def test_names_and_abi():
