@@ -47,7 +47,7 @@ namespace gznn {
 constexpr int kMaxRoles = 4;
 constexpr int kMaxSegments = 32;
 constexpr int kHeadBoards = 4;     // boards per heads_kernel workgroup (one softmax wave per board)
-constexpr int kMaxSE = 64;         // squeeze-excite units
+constexpr int kMaxSE = 128;        // squeeze-excite units (the reference's nets: filters / 3, 85 at 256)
 
 // One contiguous run of boards of a launch: its planes and outputs may live anywhere the device
 // can address (HBM, or pinned host memory of a game pool: zero-copy gather / scatter).
@@ -308,8 +308,8 @@ __host__ __device__ inline int trunk_scratch_bytes(int npos, int C, int K0, int 
     return in_stage > heads ? in_stage : heads;
 }
 __host__ __device__ inline int bias_table_bytes(int F, int B) { return align16((2 * B) * F * 4); }
-// squeeze-excite scratch: per board the channel means [F] and the compressed units [kMaxSE]
-__host__ __device__ inline int se_scratch_bytes(int F, int NB) { return NB * (F + kMaxSE) * 4; }
+// squeeze-excite scratch: per board the channel means [F] and the net's S compressed units
+__host__ __device__ inline int se_scratch_bytes(int F, int NB, int S) { return align16(NB * (F + S) * 4); }
 
 __device__ __forceinline__ float act_fn(float v, int leaky) {
     return v > 0.f ? v : (leaky ? 0.03f * v : 0.f);
@@ -843,24 +843,45 @@ __device__ __forceinline__ f32x4 board_channel_sum(const f32x4 (&acc)[Geo<F, PTN
     return s;
 }
 
-// Squeeze-excite gate of v2 block `blk` (model.py:101-126) applied in place to the conv2 output in
-// acc: per board, channel means -> Dense(S) relu -> Dense(F) sigmoid -> scale.  Two workgroup
-// barriers (every wave must reach this).  ses = LDS scratch of se_scratch_bytes(F, NB).
-template <int F, int PTN, int NB, int P>
-__device__ __forceinline__ void squeeze_excite(const KParams& kp,
-                                               f32x4 (&acc)[Geo<F, PTN, NB, P>::CT][Geo<F, PTN, NB, P>::TT], int blk,
-                                               float* ses, int co_base, int lane) {
+// Squeeze-excite gates of v2 block `blk` (model.py:101-126) from the conv2 output in acc: per board,
+// channel means -> Dense(S) relu -> Dense(F) sigmoid; gate[ct][bb] = the gates of the lane's four
+// channels of co tile ct.  ADDB: acc holds the conv without its bias (bt: the conv's bias row), which
+// is added to each value as it is summed -- the same operations as summing a biased acc, with acc
+// left untouched.  Two workgroup barriers (every wave must reach this).  ses = LDS scratch of
+// se_scratch_bytes(F, NB, S).
+template <int F, int PTN, int NB, int P, bool ADDB>
+__device__ __forceinline__ void se_gates(const KParams& kp,
+                                         const f32x4 (&acc)[Geo<F, PTN, NB, P>::CT][Geo<F, PTN, NB, P>::TT],
+                                         const float* bt, int blk, float* ses, int co_base, int lane,
+                                         f32x4 (&gate)[Geo<F, PTN, NB, P>::CT][NB]) {
     using G = Geo<F, PTN, NB, P>;
     constexpr int CT = G::CT, PT = G::PT;
     const int g = lane >> 4, li = lane & 15, npos = kp.npos, S = kp.S;
     float* mean = ses;                 // [NB][F]
-    float* hid = ses + NB * F;         // [NB][kMaxSE]
+    float* hid = ses + NB * F;         // [NB][S]
     const float inv = 1.f / (float)npos;
 #pragma unroll
     for (int bb = 0; bb < NB; ++bb)
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
-            const f32x4 s = board_channel_sum<F, PTN, NB, P>(acc, ct, bb, li, npos);
+            f32x4 s;
+            if constexpr (ADDB) {   // board_channel_sum over acc + bias
+                const float4 bias = *(const float4*)(bt + co_base + 16 * ct + 4 * g);
+                s = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int pt = 0; pt < PT; ++pt)
+                    if (16 * pt + li < npos) {
+                        f32x4 v = acc[ct][bb * PT + pt];
+                        v[0] += bias.x; v[1] += bias.y; v[2] += bias.z; v[3] += bias.w;
+                        s[0] += v[0]; s[1] += v[1]; s[2] += v[2]; s[3] += v[3];
+                    }
+#pragma unroll
+                for (int o = 1; o < 16; o <<= 1)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) s[r] += __shfl_xor(s[r], o, 64);
+            } else {
+                s = board_channel_sum<F, PTN, NB, P>(acc, ct, bb, li, npos);
+            }
             if (li == 0)
                 *(float4*)(mean + bb * F + co_base + 16 * ct + 4 * g) =
                     make_float4(s[0] * inv, s[1] * inv, s[2] * inv, s[3] * inv);
@@ -870,31 +891,63 @@ __device__ __forceinline__ void squeeze_excite(const KParams& kp,
     for (int i = threadIdx.x; i < NB * S; i += 256) {
         const int bb = i / S, j = i - bb * S;
         float h = 0.f;
+        // (one serial sum in channel order; unrolled so its weight loads go out in batches: one load
+        // per round trip made this loop most of a 256-filter block's squeeze-excite time)
+#pragma unroll 16
         for (int c = 0; c < F; ++c) h += mean[bb * F + c] * w1[c * S + j];
-        hid[bb * kMaxSE + j] = fmaxf(h, 0.f);
+        hid[bb * S + j] = fmaxf(h, 0.f);
     }
     __syncthreads();
     const float* w2 = kp.sew2 + (size_t)blk * S * F;
+    // every (co tile, board) sum in unit order, the co tiles side by side in one pass over the units
+    // (their weight loads in flight together instead of one loop of S round trips per co tile)
+    f32x4 z[CT][NB];
 #pragma unroll
-    for (int ct = 0; ct < CT; ++ct) {
-        const int co = co_base + 16 * ct + 4 * g;
+    for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+        for (int bb = 0; bb < NB; ++bb) z[ct][bb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const float* w2l = w2 + co_base + 4 * g;
+#pragma unroll 4
+    for (int j = 0; j < S; ++j) {
+        float4 w[CT];
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) w[ct] = *(const float4*)(w2l + (size_t)j * F + 16 * ct);
 #pragma unroll
         for (int bb = 0; bb < NB; ++bb) {
-            float z0 = 0.f, z1 = 0.f, z2 = 0.f, z3 = 0.f;
-            for (int j = 0; j < S; ++j) {
-                const float h = hid[bb * kMaxSE + j];
-                const float4 w = *(const float4*)(w2 + (size_t)j * F + co);
-                z0 += h * w.x; z1 += h * w.y; z2 += h * w.z; z3 += h * w.w;
-            }
-            const float g0 = 1.f / (1.f + __expf(-z0)), g1 = 1.f / (1.f + __expf(-z1));
-            const float g2 = 1.f / (1.f + __expf(-z2)), g3 = 1.f / (1.f + __expf(-z3));
+            const float h = hid[bb * S + j];
 #pragma unroll
-            for (int pt = 0; pt < PT; ++pt) {
-                f32x4& v = acc[ct][bb * PT + pt];
-                v[0] *= g0; v[1] *= g1; v[2] *= g2; v[3] *= g3;
+            for (int ct = 0; ct < CT; ++ct) {
+                z[ct][bb][0] += h * w[ct].x; z[ct][bb][1] += h * w[ct].y;
+                z[ct][bb][2] += h * w[ct].z; z[ct][bb][3] += h * w[ct].w;
             }
         }
     }
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+        for (int bb = 0; bb < NB; ++bb)
+            gate[ct][bb] = f32x4{1.f / (1.f + __expf(-z[ct][bb][0])), 1.f / (1.f + __expf(-z[ct][bb][1])),
+                                 1.f / (1.f + __expf(-z[ct][bb][2])), 1.f / (1.f + __expf(-z[ct][bb][3]))};
+}
+
+// The gates applied in place to a biased acc (the two-image kernels)
+template <int F, int PTN, int NB, int P>
+__device__ __forceinline__ void squeeze_excite(const KParams& kp,
+                                               f32x4 (&acc)[Geo<F, PTN, NB, P>::CT][Geo<F, PTN, NB, P>::TT], int blk,
+                                               float* ses, int co_base, int lane) {
+    using G = Geo<F, PTN, NB, P>;
+    constexpr int CT = G::CT, PT = G::PT;
+    f32x4 gate[CT][NB];
+    se_gates<F, PTN, NB, P, false>(kp, acc, nullptr, blk, ses, co_base, lane, gate);
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+        for (int bb = 0; bb < NB; ++bb)
+#pragma unroll
+            for (int pt = 0; pt < PT; ++pt) {
+                f32x4& v = acc[ct][bb * PT + pt];
+                v[0] *= gate[ct][bb][0]; v[1] *= gate[ct][bb][1]; v[2] *= gate[ct][bb][2]; v[3] *= gate[ct][bb][3];
+            }
 }
 
 // v2 pre-activation of the stream for block blk's first conv: act(s * scale + shift)
@@ -1043,7 +1096,9 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
     float* calp = (float*)(smem + kp.cal_off);   // [4 waves][NB][NPOS]
     // (gz_nn.hip sizes cal_off's buffer and cal_reduce sums for exactly four waves)
     static_assert(!V2 || NWV == 4, "concat_all_layers partials: four waves per group");
-    auto cal_partial = [&](int j, int bb) {
+    // (li, g: the lane's position and channel-group terms, passed in so the single-image epilogue can
+    // hand over laundered copies and the addresses below are formed per call, not kept across the conv)
+    auto cal_partial = [&](int j, int bb, int li, int g) {
         float4 wv[CT];
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) wv[ct] = *(const float4*)(kp.wcl + (size_t)j * F + co_base + 16 * ct + 4 * g);
@@ -1188,6 +1243,46 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
         const bool preact = V2 && kp.B > 0;
         f32x4* rg0 = rg;    // (residual tile addresses formed here, as in the tower's epilogues)
         if constexpr (RG) launder_ptr(rg0);
+        if constexpr (V2 && SI) {
+            // The loop below, per value the same operations, with its run-time choices as selects on
+            // data instead of branches: one uniform branch per tile for a bare initial conv and one for
+            // the pre-activation (28-44 tiles) made the register allocator split the stream's live
+            // ranges and spill them at four co tiles per wave.  A bare initial conv keeps v through the
+            // activation's select; without a residual block the image is never read, so it takes
+            // act(v) (scale 1, shift 0) instead of v.
+            const bool bare = !kp.init_act;
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) {
+                const int co = co_base + 16 * ct + 4 * g;
+                const float4 bias = *(const float4*)(kp.b0 + co);
+                float4 psc = make_float4(1.f, 1.f, 1.f, 1.f), psh = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (preact) {
+                    psc = *(const float4*)(kp.pre + co);
+                    psh = *(const float4*)(kp.pre + F + co);
+                }
+#pragma unroll
+                for (int pt = 0; pt < PT; ++pt) {
+                    f32x4 v = acc[ct][bb * PT + pt];
+                    v[0] += bias.x; v[1] += bias.y; v[2] += bias.z; v[3] += bias.w;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float a = act_fn(v[r], kp.leaky);
+                        v[r] = ((int)bare | (int)(v[r] > 0.f)) ? v[r] : a;
+                    }
+                    if constexpr (RG) rg0[(ct * TT + bb * PT + pt) * 64] = v;
+                    else resid[ct][bb * PT + pt] = v;
+                    acc[ct][bb * PT + pt] = v;    // the heads read acc when there is no residual block
+                    const f32x4 sv = pre_act(v, psc, psh, kp.leaky);
+                    if constexpr (P == 2) {
+                        static_assert(P != 2 || kLoDirect, "two-pass v2: lo parts straight to the scratch");
+                        store_act<F, PTN, 1, false>(X0 + bb * ACT, 16 * pt + li, co, sv, NPOS);
+                        store_lo_scratch<F, PTN>(xlo, 16 * pt + li, co, sv, NPOS);
+                    } else {
+                        store_act<F, PTN, P, false>(X0 + bb * ACT, 16 * pt + li, co, sv, NPOS);
+                    }
+                }
+            }
+        } else
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
             const int co = co_base + 16 * ct + 4 * g;
@@ -1220,7 +1315,7 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
             }
         }
         if constexpr (V2)
-            if (kp.cal) cal_partial(0, bb);   // layer 0: the initial conv block's output
+            if (kp.cal) cal_partial(0, bb, li, g);   // layer 0: the initial conv block's output
         __syncthreads();    // scratch is reused by the next board
         if constexpr (P == 2 && !kLoDirect) save_lo_write_hi<F, PTN>(X0, xlo, acc, NPOS, tid, co_base, li, g);
     }
@@ -1265,20 +1360,26 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
             launder(lie);
             launder(ge);
             if (V2 && second) {   // v2: s += SE(conv2 + bias); image = act(BN_1 of the next block (s))
+                // acc stays as the conv left it (in its accumulator registers) until the one pass below:
+                // the bias is added where a value is used, and the gates come back as CT x 4 registers
+                // (1.0, exact, without squeeze-excite).  A pass adding the bias in place held the whole
+                // acc in VGPRs across the gates' barriers, which spilled at four co tiles per wave.
                 const int blk = cv >> 1;
+                f32x4 gate[CT][NB];
 #pragma unroll
-                for (int ct = 0; ct < CT; ++ct) {
-                    const float4 bias = *(const float4*)(bt + co_base + 16 * ct + 4 * g);
+                for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
-                    for (int t = 0; t < TT; ++t) {
-                        acc[ct][t][0] += bias.x; acc[ct][t][1] += bias.y; acc[ct][t][2] += bias.z; acc[ct][t][3] += bias.w;
-                    }
-                }
-                if (kp.S) squeeze_excite<F, PTN, NB, P>(kp, acc, blk, (float*)(smem + kp.se_off), co_base, lane);
+                    for (int bb = 0; bb < NB; ++bb) gate[ct][bb] = f32x4{1.f, 1.f, 1.f, 1.f};
+                if (kp.S)
+                    se_gates<F, PTN, NB, P, true>(kp, acc, bt, blk, (float*)(smem + kp.se_off), co_base, 16 * ge + lie, gate);
+                // the stream add and the next block's pre-activation into the image.  After the last block
+                // nothing reads the image, so it takes act(s) (scale 1, shift 0) rather than a branch
+                // around every tile's stores.
                 const bool more = blk + 1 < kp.B;
 #pragma unroll
                 for (int ct = 0; ct < CT; ++ct) {
-                    const int co = co_base + 16 * ct + 4 * g;
+                    const int co = co_base + 16 * ct + 4 * ge;
+                    const float4 bias = *(const float4*)(bt + co);
                     float4 psc = make_float4(1.f, 1.f, 1.f, 1.f), psh = make_float4(0.f, 0.f, 0.f, 0.f);
                     if (more) {
                         psc = *(const float4*)(kp.pre + (size_t)(2 * blk + 2) * F + co);
@@ -1286,27 +1387,28 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
                     }
 #pragma unroll
                     for (int t = 0; t < TT; ++t) {
+                        const f32x4 gt = gate[ct][t / PT];
                         f32x4 v = acc[ct][t], r;
+                        v[0] += bias.x; v[1] += bias.y; v[2] += bias.z; v[3] += bias.w;
+                        v[0] *= gt[0]; v[1] *= gt[1]; v[2] *= gt[2]; v[3] *= gt[3];
                         if constexpr (RG) r = rgc[(ct * TT + t) * 64];
                         else r = resid[ct][t];
                         v[0] += r[0]; v[1] += r[1]; v[2] += r[2]; v[3] += r[3];
                         if constexpr (RG) rgc[(ct * TT + t) * 64] = v;
                         else resid[ct][t] = v;
                         acc[ct][t] = v;
-                        if (more) {
-                            const f32x4 pv = pre_act(v, psc, psh, kp.leaky);
-                            if constexpr (P == 2) {   // (two-pass split: hi parts to the image, lo to the scratch)
-                                store_act<F, PTN, 1, false>(Xe, 16 * t + lie, co, pv, NPOS);
-                                store_lo_scratch<F, PTN>(xloe, 16 * t + lie, co, pv, NPOS);
-                            } else {
-                                store_act<F, PTN, P, !G::SI>(X0, 16 * t + li, co, pv, NPOS);
-                            }
+                        const f32x4 pv = pre_act(v, psc, psh, kp.leaky);
+                        if constexpr (P == 2) {   // (two-pass split: hi parts to the image, lo to the scratch)
+                            store_act<F, PTN, 1, false>(Xe, 16 * t + lie, co, pv, NPOS);
+                            store_lo_scratch<F, PTN>(xloe, 16 * t + lie, co, pv, NPOS);
+                        } else {
+                            store_act<F, PTN, P, !G::SI>(Xe, 16 * t + lie, co, pv, NPOS);
                         }
                     }
                 }
                 if (kp.cal)   // layer blk + 1: the block's add
 #pragma unroll
-                    for (int bb = 0; bb < NB; ++bb) cal_partial(blk + 1, bb);
+                    for (int bb = 0; bb < NB; ++bb) cal_partial(blk + 1, bb, lie, ge);
                 __syncthreads();
                 if (kp.cal) cal_reduce(blk + 1);
                 continue;
@@ -1442,7 +1544,7 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
             }
             if (kp.cal)   // layer blk + 1: the block's add
 #pragma unroll
-                for (int bb = 0; bb < NB; ++bb) cal_partial(blk + 1, bb);
+                for (int bb = 0; bb < NB; ++bb) cal_partial(blk + 1, bb, li, g);
             __syncthreads();
             if (kp.cal) cal_reduce(blk + 1);
             continue;
@@ -1466,6 +1568,18 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
         }
         __syncthreads();
     }
+    // v2 single-image kernels: the heads' copy of the stream is taken from the residual here, so acc is
+    // not carried around the tower's loop (as a loop-carried value it was materialised in VGPRs at
+    // every iteration's end -- 112-176 registers beside the primed weight ring -- and spilled)
+    if constexpr (V2 && SI) {
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+            for (int t = 0; t < TT; ++t) {
+                if constexpr (RG) acc[ct][t] = rg[(ct * TT + t) * 64];
+                else acc[ct][t] = resid[ct][t];
+            }
+    }
     // the clamped tail stages are never consumed: land them before their registers are released
     if (!G::TRACKED && kp.B > 0) {
         ring_wait<0>();
@@ -1478,6 +1592,13 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
     }
 
     GZ_STAMP(2);
+    // (v2 single-image kernels: the lane's position and channel-group terms re-formed here, so the
+    // heads' per-tile addresses are not computed ahead of the tower and kept -- spilled -- across it)
+    int lih = li, gh = g;
+    if constexpr (V2 && SI) {
+        launder(lih);
+        launder(gh);
+    }
     // ---- the heads' 1x1 convs (2 per policy role + 1 value) from the fp32 residual stream (a copy
     // of the last epilogue's output is in acc);
     // features in the model's Flatten order go to the scratch for heads_kernel ----------------
@@ -1497,7 +1618,7 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
             for (int h = 0; h < kHoistHC; ++h)
 #pragma unroll
                 for (int ct = 0; ct < CT; ++ct)
-                    if (h < HC) whv[h][ct] = *(const float4*)(kp.wh + (size_t)h * F + co_base + 16 * ct + 4 * g);
+                    if (h < HC) whv[h][ct] = *(const float4*)(kp.wh + (size_t)h * F + co_base + 16 * ct + 4 * gh);
         }
     }
     // FUSE (two-image kernels): the features stay in LDS, fk = [FS][NB], and the dense heads run
@@ -1521,9 +1642,9 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
             const float inv = 1.f / (float)NPOS;
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {
-                const f32x4 sm = board_channel_sum<F, PTN, NB, P, WG>(acc, ct, bb, li, NPOS);
-                const int co = co_base + 16 * ct + 4 * g;
-                if (li == 0)
+                const f32x4 sm = board_channel_sum<F, PTN, NB, P, WG>(acc, ct, bb, lih, NPOS);
+                const int co = co_base + 16 * ct + 4 * gh;
+                if (lih == 0)
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
                         if (co + r < kp.gapF) feat_at(bb, 2 * kp.R * NPOS + co + r) = sm[r] * inv;
@@ -1533,7 +1654,7 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
         auto head_conv = [&](int h, const float4 (&wv)[CT]) {
 #pragma unroll
             for (int pt = 0; pt < PT; ++pt) {
-                const int p = 16 * pt + li;
+                const int p = 16 * pt + lih;
 #pragma unroll
                 for (int ct = 0; ct < CT; ++ct) {
                     const f32x4 a = acc[ct][bb * PT + pt];
@@ -1543,7 +1664,7 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
                     s += a[3] * wv[ct].w;
                     s += __shfl_xor(s, 16, 64);
                     s += __shfl_xor(s, 32, 64);
-                    if (g == 0 && p < NPOS) hpart[((bb * NT16 + co_base / 16 + ct) * HC + h) * NPOS + p] = s;
+                    if (gh == 0 && p < NPOS) hpart[((bb * NT16 + co_base / 16 + ct) * HC + h) * NPOS + p] = s;
                 }
             }
         };
@@ -1558,7 +1679,7 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
             for (int h = 0; h < HC; ++h) {
                 float4 wv[CT];
 #pragma unroll
-                for (int ct = 0; ct < CT; ++ct) wv[ct] = *(const float4*)(kp.wh + (size_t)h * F + co_base + 16 * ct + 4 * g);
+                for (int ct = 0; ct < CT; ++ct) wv[ct] = *(const float4*)(kp.wh + (size_t)h * F + co_base + 16 * ct + 4 * gh);
                 head_conv(h, wv);
             }
         }

@@ -202,8 +202,8 @@ __global__ void __launch_bounds__(256) se_gate_kernel(const float* u, const floa
     const float* ur = u + (size_t)row * npos * FP;
     mean[c] = sum4(ur + c, npos, FP) * (1.f / (float)npos);
     __syncthreads();
-    if (c < S) {
-        hid[c] = fmaxf(dot4(mean, 1, w1 + c, S, FP), 0.f);
+    for (int j = c; j < S; j += FP) {   // (S may exceed a narrow net's FP threads)
+        hid[j] = fmaxf(dot4(mean, 1, w1 + j, S, FP), 0.f);
     }
     __syncthreads();
     float z = 0.f;
@@ -303,7 +303,7 @@ const char* forward(const KParams& kp, const Forward& f, hipStream_t st) {
     if (!f.scratch || !f.w0 || (B > 0 && !f.wres) || !kp.feat) return "fp32 forward: missing buffer";
     if (kp.H < 1 || kp.W < 1 || kp.H > kMaxBoardSide || kp.W > kMaxBoardSide || npos != kp.H * kp.W)
         return "fp32 forward: board out of range";
-    if (padded_filters(FP) != FP || CP != pad16(kp.C) || FP > 256 || kp.S > kMaxSE || kp.S > FP)
+    if (padded_filters(FP) != FP || CP != pad16(kp.C) || FP > 256 || kp.S > kMaxSE)
         return "fp32 forward: channel counts out of range";
     if (f.chunk_rows < 1 || f.scratch_rows < (kp.n < f.chunk_rows ? kp.n : f.chunk_rows))
         return "fp32 forward: scratch rows too few";

@@ -182,7 +182,8 @@ extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
     if (!fp32 && (!kc.fn || !kl.fn)) {
         fail("unsupported network geometry F=" + std::to_string(d.cnn_filter_size) + " H=" +
              std::to_string(d.input_columns) + " W=" + std::to_string(d.input_rows) +
-             (precision == GZ_PRECISION_SPLIT ? " (split precision)" : "") + (v2 ? " (v2 nets: F <= 128)" : ""));
+             (precision == GZ_PRECISION_SPLIT ? " (split precision)" : "") + (v2 ? " (v2)" : "") +
+             (fpad == 256 ? " (F > 128: boards of up to 176 positions; larger boards run in fp32-ieee)" : ""));
         return nullptr;
     }
     gz_net* net = new gz_net;
@@ -226,7 +227,7 @@ extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
         t.resid_bytes = c.resid_bytes;
         t.smem = t.btab_off + bias_table_bytes(fpad, d.residual_layers);
         t.se_off = t.smem;
-        if (d.se_units) t.smem += se_scratch_bytes(fpad, c.nb);
+        if (d.se_units) t.smem += se_scratch_bytes(fpad, c.nb, d.se_units);
         t.cal_off = t.smem;
         if (d.concat_all_layers) t.smem += align16(4 * c.nb * npos * 4);
         return t;
@@ -285,6 +286,16 @@ extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
     kp.wmagic = (65536 + kp.W - 1) / kp.W;
     for (int r = 0; r < d.role_count; ++r) kp.P[r] = d.policy_dist_count[r];
 
+    // the last refusal that needs no device: the image, the bias table (8 F bytes per residual block)
+    // and the scratch beside them must fit the 160 KB of LDS
+    for (const gz_net::Trunk* t : {&net->small, &net->large}) {
+        if (t->smem > 160 * 1024) {
+            fail("network needs " + std::to_string(t->smem) + " B of LDS per workgroup (160 KB max): too many residual blocks "
+                 "for this board in this mode");
+            delete net;
+            return nullptr;
+        }
+    }
     if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&net->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreate(&net->ev0) != hipSuccess || hipEventCreate(&net->ev1) != hipSuccess) {
         fail(std::string("HIP init failed: ") + hipGetErrorString(hipGetLastError()));
@@ -292,11 +303,6 @@ extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
         return nullptr;
     }
     for (const gz_net::Trunk* t : {&net->small, &net->large}) {
-        if (t->smem > 160 * 1024) {
-            fail("network needs " + std::to_string(t->smem) + " B of LDS per workgroup (160 KB max)");
-            delete net;
-            return nullptr;
-        }
         if (t->smem > 64 * 1024 &&
             hipFuncSetAttribute(t->fn, hipFuncAttributeMaxDynamicSharedMemorySize, t->smem) != hipSuccess) {
             fail("cannot raise dynamic LDS limit");

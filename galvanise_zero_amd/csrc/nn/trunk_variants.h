@@ -6,8 +6,8 @@
 // positions, H and W given at run time).  Variants per geometry: NB boards per workgroup x WPE
 // workgroups per CU ("11", "12", "21"), and the split-precision kernel (P = 3, one board per
 // workgroup, boards of up to 64 positions).  v2 (pre-activation / squeeze-excite) nets use the
-// trunk_kernel_v2 instantiations of the same variants (trunk_f64_v2.hip, trunk_f128_v2.hip; the
-// reference's v2 nets have at most 128 filters).
+// trunk_kernel_v2 instantiations of the same variants (trunk_f64_v2.hip, trunk_f128_v2.hip and
+// trunk_f256_v2.hip: 256 filters on position tiles 4, 7 and 11, one board per workgroup as for v1).
 #pragma once
 
 #include "forward_kernel.h"
@@ -89,7 +89,7 @@ KernelChoice variants(int v, int precision) {
             if constexpr (Geo<F, PTN, 1, 3>::SI && Geo<F, PTN, 1, 3>::ACT_BYTES + 40 * 1024 <= 160 * 1024 &&
                           !Geo<F, PTN, 1, 3>::RG) {
                 if (v == 11) return kernel_for<F, PTN, 1, 1, 3, V2>();
-            } else if constexpr (!V2 && Geo<F, PTN, 1, 2>::SI && Geo<F, PTN, 1, 2>::ACT_BYTES + 16 * 1024 <= 160 * 1024) {
+            } else if constexpr (Geo<F, PTN, 1, 2>::SI && Geo<F, PTN, 1, 2>::ACT_BYTES + 16 * 1024 <= 160 * 1024) {
                 if (v == 11) return kernel_for<F, PTN, 1, 1, 2, V2>();
             }
             return KernelChoice{};
@@ -138,6 +138,7 @@ KernelChoice trunk_variant_f128(int pt, int v, int precision);
 KernelChoice trunk_variant_f256(int pt, int v, int precision);
 KernelChoice trunk_variant_f64_v2(int pt, int v, int precision);
 KernelChoice trunk_variant_f128_v2(int pt, int v, int precision);
+KernelChoice trunk_variant_f256_v2(int pt, int v, int precision);
 
 // padded filter count and position tiles of a board; 0 when not compiled
 inline int padded_filters(int F) { return F <= 64 ? 64 : F <= 128 ? 128 : F <= 256 ? 256 : 0; }
@@ -156,6 +157,7 @@ inline KernelChoice trunk_variant(int fpad, int pt, int v, int precision, bool v
     if (v2) {
         if (fpad == 64) return trunk_variant_f64_v2(pt, v, precision);
         if (fpad == 128) return trunk_variant_f128_v2(pt, v, precision);
+        if (fpad == 256) return trunk_variant_f256_v2(pt, v, precision);
         return KernelChoice{};
     }
     if (fpad == 64) return trunk_variant_f64(pt, v, precision);

@@ -37,6 +37,13 @@ error is 1.9-3.7e-7 against bf16x3's 2.7-5.1e-6.  It costs 4.2x a bf16x3 forward
 it for match play, gating games and for separating a wrong net from a saturated softmax moved by
 the split arithmetic; the constants below are bf16x3's.
 
+v2 nets with 256 filters (tests/test_nn_v2_f256_gpu.py: two-block nets on 8 x 8, 10 x 10 and 13 x 13,
+85 squeeze-excite units, damped weights, 1 and 7 rows; profiles/v2_f256_gpu_tests.log) are asserted
+against the 256-filter constants below: bf16x3's relative logit error is at most 7.2e-6 against the
+cfg4 bound of 1.2e-4, its probabilities within max 8.9e-7 / mean 4.0e-7 / row KL 1.1e-7 against
+DAMPED_TOLERANCE; bf16 errs at most 1.0e-3 / 4.6e-4 (its 128-filter twins: 8.2e-4 / 4.2e-4);
+fp32-ieee 1.2e-7 / 3.2e-8 with a relative logit error of 2.9e-7.
+
 The north-star tolerance per config, then:
   cfg2, cfg3   the probability bounds below (max / mean / KL), on the bench's weights
   cfg4, cfg5   the relative logits bound below on the bench's (saturating) weights, and in probability

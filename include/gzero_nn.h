@@ -46,14 +46,21 @@ typedef struct gz_net_desc {
      *   accumulation: pre-softmax logits within ~1e-4 relative of an fp32 forward, the per-config
      *   bounds of nn/tolerance.py); F <= 128 on boards <= 64 positions two per workgroup, larger
      *   boards (up to 19 x 19) one per workgroup, by two passes per conv where the hi + lo image
-     *   exceeds the LDS (F = 256 on 13 x 13, F = 128 on 19 x 19).  The heads' 1x1 convs, softmaxes and value MLP are
+     *   exceeds the LDS (F = 256 on 13 x 13, F = 128 on 19 x 19; v2 nets with F = 256 also on
+     *   8 x 8).  F = 256 (any filter count from 129 up, padded), v1 and v2, runs on boards of up
+     *   to 176 positions (13 x 13) in both modes, as deep as the image, the bias table (2,048
+     *   bytes per residual block) and the squeeze-excite / concat_all_layers scratch fit the
+     *   160 KB of LDS -- 13 blocks on 13 x 13 (12 with squeeze-excite), 20 on 10 x 10 in the split
+     *   mode, 37 in bf16; gz_net_create refuses a deeper net before any device call
+     *   ("network needs ... B of LDS").  The heads' 1x1 convs, softmaxes and value MLP are
      *   fp32 in both modes; the policy Dense is fp32 except for single-image nets with a policy of
      *   >= 512 moves (amazons), whose policy Dense of the whole launch runs as one bf16x3 split MFMA
      *   GEMM in both modes (policy_gemm_kernel; GZ_NO_GEMM_HEADS=1 keeps it fp32 on the VALU).
      *   GZ_PRECISION_FP32 (4): IEEE fp32, the reference's arithmetic -- every conv on the f32-input
      *   MFMA (v_mfma_f32_16x16x4_f32: f32 operands, f32 accumulation, a k-ordered fmaf chain), BN
      *   folded in fp32, fp32 activations.  The trunk runs layer by layer through a device scratch
-     *   (no LDS-image limit: every board up to 19 x 19 with F <= 256, v1 and v2), large launches in
+     *   (no LDS-image limit: every board up to 19 x 19 with F <= 256, v1 and v2 with up to 128
+     *   squeeze-excite units, any depth), large launches in
      *   sequential row chunks; the heads kernel follows and the policy Dense is always fp32.  About
      *   16/3 of the split mode's MFMA time: for match play, gating and numerics checks, not for
      *   self-play throughput.  Every row's outputs are bit-identical whatever the launch.
@@ -64,7 +71,7 @@ typedef struct gz_net_desc {
     int resnet_v2;                            /* blocks BN-act-conv-BN-act-conv [SE], add, no act    */
     int initial_kernel;                       /* 1 or 3; 0 = model.py's (1 for v2, 3 for v1)        */
     int initial_bn;                           /* v2: BN + act after the initial conv (0: bare conv)  */
-    int se_units;                             /* squeeze-excite compress units, 0 = none (<= 64)     */
+    int se_units;                             /* squeeze-excite compress units, 0 = none (<= 128)    */
     int global_pooling_value;                 /* value features = [trunk channel means (F), conv (HW)] */
     /* v2 only, model.py:251-260: the value head reads every trunk layer (the initial conv block's
      * output and each residual block's add), each through its own 1x1 conv + BN + act: (B + 1) HW
