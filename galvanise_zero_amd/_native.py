@@ -65,23 +65,30 @@ class GzNetDesc(ctypes.Structure):
 GZ_PRECISION_BF16 = 1
 GZ_PRECISION_SPLIT = 3
 GZ_PRECISION_FP32 = 4
+GZ_PRECISION_BF16_LAYERED = 5
+GZ_PRECISION_SPLIT_LAYERED = 6
 # "bf16x3" (alias "split"): each fp32 operand as bf16 hi + lo, three MFMAs per product, ~16
 # significant bits per operand -- fp32-CLASS, not IEEE fp32: on the headline cfg2 batch its error
 # against the float64 oracle is ~35x an IEEE fp32 forward's (nn/tolerance.py).  "fp32" is the
 # pre-round-6 name of the same mode, kept as a deprecated alias.
 # "fp32-ieee": the reference's arithmetic -- every conv on the f32-input MFMA (f32 operands and
 # accumulation), layer by layer through a device scratch; about 16/3 of bf16x3's MFMA time.
+# "bf16-layered" / "bf16x3-layered": the arithmetic of "bf16" / "bf16x3" for the nets those refuse
+# (more than 128 filters on a board above 13 x 13, more residual blocks than their LDS image leaves
+# room for): the trunk layer by layer through HBM like fp32-ieee's, its convs on the bf16 MFMA.
 PRECISIONS = {"bf16": GZ_PRECISION_BF16, "bf16x3": GZ_PRECISION_SPLIT, "split": GZ_PRECISION_SPLIT,
-              "fp32": GZ_PRECISION_SPLIT, "fp32-ieee": GZ_PRECISION_FP32}
-_CANONICAL = {GZ_PRECISION_BF16: "bf16", GZ_PRECISION_SPLIT: "bf16x3", GZ_PRECISION_FP32: "fp32-ieee"}
+              "fp32": GZ_PRECISION_SPLIT, "fp32-ieee": GZ_PRECISION_FP32,
+              "bf16-layered": GZ_PRECISION_BF16_LAYERED, "bf16x3-layered": GZ_PRECISION_SPLIT_LAYERED}
+_CANONICAL = {GZ_PRECISION_BF16: "bf16", GZ_PRECISION_SPLIT: "bf16x3", GZ_PRECISION_FP32: "fp32-ieee",
+              GZ_PRECISION_BF16_LAYERED: "bf16-layered", GZ_PRECISION_SPLIT_LAYERED: "bf16x3-layered"}
 
 
 def canonical_precision(precision):
-    """The arithmetic mode's canonical name ("bf16", "bf16x3" or "fp32-ieee"); "split" and the
-    deprecated "fp32" name bf16x3."""
+    """The arithmetic mode's canonical name ("bf16", "bf16x3", "fp32-ieee", "bf16-layered" or
+    "bf16x3-layered"); "split" and the deprecated "fp32" name bf16x3."""
     if precision not in PRECISIONS:
-        raise ValueError("precision %r: one of bf16, bf16x3 (alias split), fp32-ieee (fp32 is a deprecated "
-                         "alias of bf16x3)" % (precision,))
+        raise ValueError("precision %r: one of bf16, bf16x3 (alias split), fp32-ieee, bf16-layered, bf16x3-layered "
+                         "(fp32 is a deprecated alias of bf16x3)" % (precision,))
     if precision == "fp32":
         import warnings
         warnings.warn('precision "fp32" selects the bf16x3 split mode (three bf16 MFMAs per product, '
@@ -180,7 +187,11 @@ class HipNet(object):
     fp32, include/gzero_nn.h GZ_PRECISION_SPLIT) or "fp32-ieee" (GZ_PRECISION_FP32: IEEE fp32 like
     the reference, on the f32-input MFMA, layer by layer through device memory -- every geometry up
     to 19 x 19 / 256 filters, bit-identical rows whatever the batch; several times slower than
-    bf16x3: for match play, gating and numerics checks).  "fp32" is a deprecated alias of "bf16x3";
+    bf16x3: for match play, gating and numerics checks), or "bf16-layered" / "bf16x3-layered"
+    (GZ_PRECISION_BF16_LAYERED / _SPLIT_LAYERED: bf16's / bf16x3's arithmetic and weight image on
+    fp32-ieee's layer-by-layer trunk, for the nets the fused modes refuse -- F > 128 above 13 x 13,
+    or deeper than their LDS image allows; slower than the fused modes where those run).
+    "fp32" is a deprecated alias of "bf16x3";
     self.precision holds the canonical name."""
 
     def __init__(self, desc, device=0, precision="bf16"):

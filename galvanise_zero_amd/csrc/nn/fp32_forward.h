@@ -5,6 +5,8 @@
 //   * the index arithmetic the conv kernel, the weight packing (weight_image.h) and the CPU check
 //     (tests/fp32_host_check.cpp) share -- plain C++, usable without a HIP compiler;
 //   * the launch interface gz_nn.hip calls (HIP compilers only).
+// The layer loop (forward), the scratch and every kernel but the conv and the input gather also serve
+// the layered bf16 modes (layered_forward.h, Forward::parts).
 //
 // The 3x3 conv as an implicit GEMM  out[co][c] = sum_{tap,ci} W[co][tap,ci] * X[nbr(c,tap)][ci]:
 // its columns c are the launch's board positions, flat: c = row * npos + p over the NHWC
@@ -121,16 +123,37 @@ GZF_HD inline int chunk_count(int n, int chunk_rows) { return (n + chunk_rows - 
 
 namespace gzfp32 {
 
+// One conv launch of the layer loop
+struct ConvArgs {
+    const float* x;        // [ncols][cinp]
+    const void* w;         // fp32: wfrag_index order; layered: the bf16 image (hi parts, or hi | lo fragments)
+    const float* bias;     // [FP]
+    const float* skip;     // [ncols][FP] added before the activation, or nullptr (may alias out)
+    float* out;            // [ncols][FP]
+    float* out2;           // v2: act(out * psc + psh), the next block's pre-activation image, or nullptr
+    const float* psc;
+    const float* psh;
+    int ncols, cinp, taps, FP, H, W, npos, act, leaky;
+    // the layered modes (layered_forward.h)
+    const void* wlo;       // the initial conv's lo image (parts == 3)
+    int parts;             // 1: bf16, 3: split
+    int w0_layout;         // w is the initial conv's [K0 / 32][FP][32] image (taps == 1, cinp == K0)
+};
+
 // What a launch needs beyond KParams (whose weight pointers b0, bres, wh, bh, wcl, bcl, pre, sew1,
 // sew2, segment table and feature scratch it reads as the bf16 kernels do)
 struct Forward {
     const float* w0 = nullptr;     // initial conv image [taps0][CP / 16][FP / 16][64][4]
     const float* wres = nullptr;   // trunk conv images [2B][9][FP / 16][FP / 16][64][4]
-    int CP = 0, FP = 0;            // padded input planes / filters
+    int CP = 0, FP = 0;            // input channels of the initial conv's launch (fp32: the planes padded to
+                                   // 16; layered: K0, the im2col image's width) / padded filters
     int chunk_rows = 1;            // rows per sequential chunk
     char* scratch = nullptr;       // scratch_layout(scratch_rows, ...) bytes
     int scratch_rows = 0;
     size_t scratch_bytes = 0;
+    // The layered modes (layered_forward.h) run the same layer loop with their own conv and input
+    // gather: parts = 1 (bf16) or 3 (split), the weights kp.w0 / kp.w0lo / kp.wres; 0: the fp32 conv
+    int parts = 0;
 };
 
 // Queues the trunk of kp.n rows on `stream`: gather, convs, squeeze-excite, the head features into

@@ -2,6 +2,7 @@
 // kernel), squeeze-excite, the head features.  Everything but the conv is plain HIP with one thread
 // per output and a sum in fixed order (four interleaved partial sums), no atomics.
 #include "fp32_forward.h"
+#include "layered_forward.h"
 
 #include <hip/hip_runtime.h>
 
@@ -31,18 +32,6 @@ __global__ void __launch_bounds__(256) gather_kernel(const KParams kp, float* in
 }  // namespace
 
 // ---- the conv (named gzfp32::conv_f32_kernel<CT>: conv_kernel_name) -------------------------------
-struct ConvArgs {
-    const float* x;        // [ncols][cinp]
-    const float* w;        // wfrag_index order
-    const float* bias;     // [FP]
-    const float* skip;     // [ncols][FP] added before the activation, or nullptr (may alias out)
-    float* out;            // [ncols][FP]
-    float* out2;           // v2: act(out * psc + psh), the next block's pre-activation image, or nullptr
-    const float* psc;
-    const float* psh;
-    int ncols, cinp, taps, FP, H, W, npos, act, leaky;
-};
-
 template <int CT>
 __global__ void __launch_bounds__(256) conv_f32_kernel(const ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -98,7 +87,7 @@ __global__ void __launch_bounds__(256) conv_f32_kernel(const ConvArgs a) {
             int row[TT];
 #pragma unroll
             for (int t = 0; t < TT; ++t) row[t] = nbr_row(a.H, W, ys[t], xs[t], tap, tc0 + 16 * t + li, live[t]) * stride + 4 * g;
-            const float* wt = a.w + (((size_t)tp * (cinp >> 4) + (kc >> 4)) * cotiles + (co_wave >> 4)) * 256 + 4 * lane;
+            const float* wt = (const float*)a.w + (((size_t)tp * (cinp >> 4) + (kc >> 4)) * cotiles + (co_wave >> 4)) * 256 + 4 * lane;
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
@@ -300,49 +289,63 @@ const char* forward(const KParams& kp, const Forward& f, hipStream_t st) {
     const int npos = kp.npos, FP = f.FP, CP = f.CP, B = kp.B;
     // every size the kernels rely on, before anything is launched
     if (kp.n < 1) return nullptr;
-    if (!f.scratch || !f.w0 || (B > 0 && !f.wres) || !kp.feat) return "fp32 forward: missing buffer";
+    const bool layered = f.parts != 0;   // the conv and the input gather of layered_forward.h
+    if (layered && f.parts != 1 && f.parts != 3) return "fp32 forward: bad part count";
+    if (layered ? (!kp.w0 || (f.parts == 3 && !kp.w0lo) || (B > 0 && !kp.wres)) : (!f.w0 || (B > 0 && !f.wres)))
+        return "fp32 forward: missing weights";
+    if (!f.scratch || !kp.feat) return "fp32 forward: missing buffer";
     if (kp.H < 1 || kp.W < 1 || kp.H > kMaxBoardSide || kp.W > kMaxBoardSide || npos != kp.H * kp.W)
         return "fp32 forward: board out of range";
-    if (padded_filters(FP) != FP || CP != pad16(kp.C) || FP > 256 || kp.S > kMaxSE)
+    if (padded_filters(FP) != FP || CP != (layered ? kp.K0 : pad16(kp.C)) || FP > 256 || kp.S > kMaxSE)
         return "fp32 forward: channel counts out of range";
     if (f.chunk_rows < 1 || f.scratch_rows < (kp.n < f.chunk_rows ? kp.n : f.chunk_rows))
         return "fp32 forward: scratch rows too few";
     if ((size_t)f.scratch_rows * npos > ((size_t)1 << 31) / 260) return "fp32 forward: chunk too large";
     const ScratchLayout L = scratch_layout(f.scratch_rows, npos, CP, FP);
     if (L.total > f.scratch_bytes) return "fp32 forward: scratch too small";
-    if (lds_bytes(kp.W) > 64 * 1024) return "fp32 forward: LDS image too large";
+    if ((layered ? gzlayered::lds_bytes(kp.W, f.parts) : lds_bytes(kp.W)) > 64 * 1024) return "fp32 forward: LDS image too large";
     float* in = (float*)(f.scratch + L.in);
     float* S = (float*)(f.scratch + L.s);
     float* T = (float*)(f.scratch + L.t);
     float* X = (float*)(f.scratch + L.x);
     float* gate = (float*)(f.scratch + L.gate);
     const bool v2 = kp.v2 != 0;
-    const size_t conv_floats = conv_image_floats(9, FP, FP);
+    // one trunk conv's image: fp32 in wfrag_index order, or the fused modes' bf16 fragments (hi | lo)
+    const char* wres = layered ? (const char*)kp.wres : (const char*)f.wres;
+    const size_t conv_bytes = layered ? (size_t)gzlayered::operand_parts(f.parts) * 9 * FP * FP * 2 : conv_image_floats(9, FP, FP) * 4;
 
     for (int ck = 0; ck < chunk_count(kp.n, f.chunk_rows); ++ck) {
         int row0, rows;
         chunk_bounds(kp.n, f.chunk_rows, ck, &row0, &rows);
         if (rows < 1 || rows > f.scratch_rows) return "fp32 forward: chunk bounds";
         const int ncols = rows * npos;
-        hipLaunchKernelGGL(gather_kernel, dim3(blocks_for((size_t)ncols * CP)), dim3(256), 0, st, kp, in, row0, rows, CP);
+        if (layered) gzlayered::launch_im2col(kp, in, row0, rows, st);
+        else hipLaunchKernelGGL(gather_kernel, dim3(blocks_for((size_t)ncols * CP)), dim3(256), 0, st, kp, in, row0, rows, CP);
         ConvArgs a{};
+        a.parts = f.parts;
         a.ncols = ncols; a.FP = FP; a.H = kp.H; a.W = kp.W; a.npos = npos; a.leaky = kp.leaky;
-        auto conv = [&](const float* x, const float* w, const float* bias, int cinp, int taps, const float* skip, float* out,
+        auto conv = [&](const float* x, const void* w, const float* bias, int cinp, int taps, const float* skip, float* out,
                         int act, float* out2, int pre_blk) {
             a.x = x; a.w = w; a.bias = bias; a.cinp = cinp; a.taps = taps; a.skip = skip; a.out = out; a.act = act;
             a.out2 = out2;
             a.psc = out2 ? kp.pre + (size_t)(2 * pre_blk) * FP : nullptr;
             a.psh = out2 ? kp.pre + (size_t)(2 * pre_blk + 1) * FP : nullptr;
-            return launch_conv(a, st);
+            return layered ? gzlayered::launch_conv(a, st) : launch_conv(a, st);
         };
         const char* e;
         // initial conv: the stream s (v1: activated; v2: + the first block's pre-activation image)
-        if ((e = conv(in, f.w0, kp.b0, CP, kp.k0taps, nullptr, S, (!v2 || kp.init_act) ? 1 : 0, (v2 && B > 0) ? X : nullptr, 0)))
-            return e;
+        // (layered: a 1-tap conv over the im2col image, its weights the [K0 / 32][FP][32] image)
+        a.w0_layout = layered ? 1 : 0;
+        a.wlo = layered ? kp.w0lo : nullptr;
+        e = conv(in, layered ? (const void*)kp.w0 : (const void*)f.w0, kp.b0, CP, layered ? 1 : kp.k0taps, nullptr, S,
+                 (!v2 || kp.init_act) ? 1 : 0, (v2 && B > 0) ? X : nullptr, 0);
+        a.w0_layout = 0;
+        a.wlo = nullptr;
+        if (e) return e;
         if (kp.cal) hipLaunchKernelGGL(layer_conv_kernel, dim3(blocks_for(ncols)), dim3(256), 0, st, kp, S, row0, rows, FP, 0);
         for (int blk = 0; blk < B; ++blk) {
-            const float* w1 = f.wres + (size_t)(2 * blk) * conv_floats;
-            const float* w2 = w1 + conv_floats;
+            const char* w1 = wres + (size_t)(2 * blk) * conv_bytes;
+            const char* w2 = w1 + conv_bytes;
             const float* b1 = kp.bres + (size_t)(2 * blk) * FP;
             const float* b2 = b1 + FP;
             if (!v2) {   // s = act(conv2(act(conv1(s))) + s)

@@ -7,6 +7,7 @@
 #include "forward_kernel.h"
 #include "trunk_variants.h"
 #include "fp32_forward.h"
+#include "layered_forward.h"
 #include "weight_image.h"
 #include "../../../include/gzero_nn.h"
 
@@ -81,6 +82,10 @@ struct gz_net : PackSpec {         // d, fpad, p2, K0, cp, fp32, gemm_heads: wha
     const float* w0f = nullptr;
     const float* wresf = nullptr;
     std::map<hipStream_t, std::pair<char*, int>> fscr;   // scratch and the rows it holds
+    // GZ_PRECISION_BF16_LAYERED / _SPLIT_LAYERED (layered_forward.h): the same layer-wise trunk and scratch
+    // with the bf16 conv over the fused modes' weight image; 1 (bf16) or 3 (split) parts, 0: another mode
+    int layered = 0;
+    int in_width() const { return layered ? K0 : cp; }   // input channels of the initial conv's launch
 };
 
 extern "C" const char* gz_nn_last_error(void) { return g_err.c_str(); }
@@ -130,7 +135,9 @@ extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
     }
     const int precision = d.precision == 0 ? GZ_PRECISION_BF16 : d.precision;
     const bool fp32 = precision == GZ_PRECISION_FP32;
-    if (precision != GZ_PRECISION_BF16 && precision != GZ_PRECISION_SPLIT && !fp32) { fail("unknown precision"); return nullptr; }
+    const int layered = precision == GZ_PRECISION_BF16_LAYERED ? 1 : precision == GZ_PRECISION_SPLIT_LAYERED ? 3 : 0;
+    const bool layerwise = fp32 || layered;   // the trunk layer by layer through HBM: no LDS-image limit
+    if (precision != GZ_PRECISION_BF16 && precision != GZ_PRECISION_SPLIT && !layerwise) { fail("unknown precision"); return nullptr; }
     int vs = kSmallVariant, vl = kLargeVariant, min_large = kLargeMinRows;
     if (const char* e = getenv("GZ_KERNEL_VARIANT")) {   // experiments: one fixed variant
         vs = vl = atoi(e);
@@ -143,19 +150,19 @@ extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
     const int fpad = fp32 ? gzfp32::padded_filters(d.cnn_filter_size) : kernel_filters(d.cnn_filter_size, (npos_ + 15) / 16);
     if (d.input_rows > 32 || npos_ >= 1024) { fail("board too large"); return nullptr; }
     const bool v2 = d.resnet_v2 != 0;
-    if (fp32) {
-        // the layer-wise fp32 path has no LDS-image limit: any board up to 19 x 19, F <= 256, v1 or v2
+    if (layerwise) {
+        // the layer-wise paths have no LDS-image limit: any board up to 19 x 19, F <= 256, v1 or v2
         if (d.input_columns < 1 || d.input_rows < 1 || d.input_columns > gzfp32::kMaxBoardSide ||
             d.input_rows > gzfp32::kMaxBoardSide || fpad == 0 || d.input_channels < 1) {
             fail("unsupported network geometry F=" + std::to_string(d.cnn_filter_size) + " H=" +
                  std::to_string(d.input_columns) + " W=" + std::to_string(d.input_rows) +
-                 " (fp32-ieee: boards up to 19 x 19, F <= 256)");
+                 (fp32 ? " (fp32-ieee: boards up to 19 x 19, F <= 256)" : " (layered modes: boards up to 19 x 19, F <= 256)"));
             return nullptr;
         }
         min_large = 1 << 30;   // one conv kernel for every launch size
     }
-    KernelChoice kc = fp32 ? KernelChoice{} : select_kernel(fpad, pt, vs, precision, v2);
-    KernelChoice kl = fp32 ? KernelChoice{} : select_kernel(fpad, pt, vl, precision, v2);
+    KernelChoice kc = layerwise ? KernelChoice{} : select_kernel(fpad, pt, vs, precision, v2);
+    KernelChoice kl = layerwise ? KernelChoice{} : select_kernel(fpad, pt, vl, precision, v2);
     if (!kl.fn && vl == kLargeVariant) kl = select_kernel(fpad, pt, kLargeFallback, precision, v2);
     // wave-group kernels: each group's staging / heads scratch must fit its own image
     auto wg_fits = [&](const KernelChoice& c) {
@@ -179,7 +186,7 @@ extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
         kl = kc;
         min_large = 1 << 30;
     }
-    if (!fp32 && (!kc.fn || !kl.fn)) {
+    if (!layerwise && (!kc.fn || !kl.fn)) {
         fail("unsupported network geometry F=" + std::to_string(d.cnn_filter_size) + " H=" +
              std::to_string(d.input_columns) + " W=" + std::to_string(d.input_rows) +
              (precision == GZ_PRECISION_SPLIT ? " (split precision)" : "") + (v2 ? " (v2)" : "") +
@@ -190,17 +197,14 @@ extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
     net->d = d;
     net->device = device;
     net->large_min_rows = min_large;
-    net->p2 = precision == GZ_PRECISION_SPLIT ? 2 : 1;
-    net->fpad = fpad;
-    net->fp32 = fp32;
-    net->cp = gzfp32::pad16(d.input_channels);
-    if (fp32) {
-        net->chunk_rows = gzfp32::chunk_rows_for(npos_, net->cp, fpad);
+    static_cast<PackSpec&>(*net) = pack_spec(d, precision, fpad, false);   // (gemm_heads: below)
+    net->layered = layered;
+    const int k0 = initial_kernel(d);
+    if (layerwise) {
+        net->chunk_rows = gzfp32::chunk_rows_for(npos_, net->in_width(), fpad);
         if (const char* e = getenv("GZ_FP32_CHUNK_ROWS"))   // tests: chunking without a large launch
             net->chunk_rows = std::max(1, std::min(atoi(e), net->chunk_rows));
     }
-    const int k0 = initial_kernel(d);
-    net->K0 = ((k0 * k0 * d.input_channels + 31) / 32) * 32;
     net->nweights = blob_plan(d).consumed;
     int maxP = 0;
     for (int r = 0; r < d.role_count; ++r) maxP = std::max(maxP, d.policy_dist_count[r]);
@@ -236,9 +240,9 @@ extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
     for (int pass = 0; pass < 2; ++pass) {
         net->small = trunk(kc);
         net->large = trunk(kl);
-        if (fp32) {   // no trunk kernel: fp32_forward.hip's launches, then heads_kernel
+        if (layerwise) {   // no trunk kernel: fp32_forward.hip's launches, then heads_kernel
             gz_net::Trunk t;
-            t.name = gzfp32::conv_kernel_name(fpad);
+            t.name = layered ? gzlayered::conv_kernel_name(fpad, layered) : gzfp32::conv_kernel_name(fpad);
             net->small = net->large = t;
         }
         net->heads_smem = heads_lds_bytes(FS, lgrow);
@@ -560,11 +564,16 @@ static int launch_segments(gz_net* net, hipStream_t stream, const gz_segment* se
             kp.glog = g.first;
         }
     }
-    if (net->fp32) {   // the layer-wise fp32 trunk (fp32_forward.hip), then the heads kernel (blocked Dense sums)
+    if (net->fp32 || net->layered) {
+        // the layer-wise trunk (fp32_forward.hip), then the heads: fp32-ieee's kernel with blocked Dense
+        // sums, the layered modes' as after a single-image bf16 / bf16x3 trunk
         gzfp32::Forward f;
-        f.w0 = net->w0f;
-        f.wres = net->wresf;
-        f.CP = net->cp;
+        f.parts = net->layered;
+        if (net->fp32) {
+            f.w0 = net->w0f;
+            f.wres = net->wresf;
+        }
+        f.CP = net->in_width();
         f.FP = net->fpad;
         f.chunk_rows = net->chunk_rows;
         {   // this stream's activation scratch (grown with a device sync: rare, sizes only increase)
@@ -590,8 +599,14 @@ static int launch_segments(gz_net* net, hipStream_t stream, const gz_segment* se
         if (const char* e = gzfp32::forward(kp, f, stream)) return fail(e);
         if (mid) HIPCHK(hipEventRecord(mid, stream));
         void* hargs[] = {&kp};
-        HIPCHK(hipLaunchKernel((const void*)&heads_kernel_blocked, dim3((n + kHeadBoards - 1) / kHeadBoards), dim3(256), hargs,
-                               net->heads_smem, stream));
+        if (net->gemm_heads) {
+            int maxjt = 0;
+            for (int r = 0; r < kp.R; ++r) maxjt = std::max(maxjt, (kp.P[r] + 15) / 16);
+            HIPCHK(hipLaunchKernel((const void*)&policy_gemm_kernel, dim3((n + 63) / 64, (maxjt + 7) / 8, kp.R), dim3(256),
+                                   hargs, 0, stream));
+        }
+        HIPCHK(hipLaunchKernel(net->fp32 ? (const void*)&heads_kernel_blocked : (const void*)&heads_kernel,
+                               dim3((n + kHeadBoards - 1) / kHeadBoards), dim3(256), hargs, net->heads_smem, stream));
         return 0;
     }
     const gz_net::Trunk& t = n >= net->large_min_rows ? net->large : net->small;
@@ -714,7 +729,8 @@ extern "C" int gz_net_forward(gz_net* net, const float* planes, int n, float* co
 }
 
 extern "C" int gz_net_stamp_avg(const gz_net* net, double* out8) {
-    if (net && net->fp32) return fail("no kernel stamps in fp32-ieee mode (the trunk is many launches)");
+    if (net && (net->fp32 || net->layered))
+        return fail("no kernel stamps in the fp32-ieee and layered modes (the trunk is many launches)");
     for (int i = 0; i < 8; ++i) out8[i] = net->stamp_avg[i];
     return 0;
 }
@@ -737,7 +753,7 @@ extern "C" const char* gz_net_kernel_name(const gz_net* net, int large) {
 
 extern "C" int gz_net_wave_rows(const gz_net* net) {
     if (!net) return 0;
-    if (net->fp32) {   // rows whose conv grid is one workgroup per CU
+    if (net->fp32 || net->layered) {   // rows whose conv grid is one workgroup per CU
         const int gy = net->fpad / (32 * gzfp32::wave_co_tiles(net->fpad));
         return std::max(1, (kCUs / gy) * gzfp32::kTileCols / net->kp.npos);
     }

@@ -47,6 +47,20 @@ struct PackSpec {
 inline int initial_kernel(const gz_net_desc& d) {
     return d.initial_kernel ? d.initial_kernel : (d.resnet_v2 ? 1 : d.cnn_kernel_size);
 }
+// The spec of desc d in arithmetic mode `precision` (gz_net_desc.precision, not 0) with fpad padded
+// filters.  The layered modes pack the image of the fused mode with the same operand parts: the two
+// specs are equal, so are the images.
+inline PackSpec pack_spec(const gz_net_desc& d, int precision, int fpad, bool gemm_heads) {
+    PackSpec s;
+    s.d = d;
+    s.fpad = fpad;
+    s.p2 = (precision == GZ_PRECISION_SPLIT || precision == GZ_PRECISION_SPLIT_LAYERED) ? 2 : 1;
+    s.K0 = ((initial_kernel(d) * initial_kernel(d) * d.input_channels + 31) / 32) * 32;
+    s.cp = (d.input_channels + 15) & ~15;
+    s.fp32 = precision == GZ_PRECISION_FP32;
+    s.gemm_heads = gemm_heads;
+    return s;
+}
 inline bool has_initial_bn(const gz_net_desc& d) { return !d.resnet_v2 || d.initial_bn; }
 inline int gap_features(const gz_net_desc& d) { return d.global_pooling_value ? d.cnn_filter_size : 0; }
 // trunk layers the concat_all_layers value head reads (model.py:251-260), 0 for the other heads

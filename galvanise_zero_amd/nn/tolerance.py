@@ -44,6 +44,17 @@ cfg4 bound of 1.2e-4, its probabilities within max 8.9e-7 / mean 4.0e-7 / row KL
 DAMPED_TOLERANCE; bf16 errs at most 1.0e-3 / 4.6e-4 (its 128-filter twins: 8.2e-4 / 4.2e-4);
 fp32-ieee 1.2e-7 / 3.2e-8 with a relative logit error of 2.9e-7.
 
+The layered modes ("bf16-layered" / "bf16x3-layered": bf16's / bf16x3's operands and products on
+fp32-ieee's layer-by-layer trunk, for the nets the fused kernels refuse) are asserted against the
+same constants (tests/test_nn_layered_gpu.py; damped weights, 1-7 rows): bf16x3-layered's relative
+logit error against LOGITS_TOL = 1.2e-4 and, where the fused bf16x3 runs the net, 3 x the fused
+mode's; its probabilities against DAMPED_TOLERANCE; bf16-layered per output against max(TOL_V2_BF16,
+3 x the fused bf16 error of the net or of its fused-size twin).  Measured on MI355X (profiles/layered_gpu_tests.txt):
+bf16x3-layered probabilities within max 1.62e-6 / mean 1.13e-6 / row KL 1.16e-7, relative logit error
+at most 2.91e-5 (both on the 13 x 13 v1 net of 14 x 256, 2 rows; 2.8-7.2e-6 on the two-block nets,
+0.76-1.01 x the fused bf16x3's on the same rows); bf16-layered max 1.04e-3 (6 x 9 legacy net, 7 rows), equal to
+the fused bf16's on the same rows to the printed digits on every net both run.
+
 The north-star tolerance per config, then:
   cfg2, cfg3   the probability bounds below (max / mean / KL), on the bench's weights
   cfg4, cfg5   the relative logits bound below on the bench's (saturating) weights, and in probability

@@ -64,7 +64,18 @@ typedef struct gz_net_desc {
      *   sequential row chunks; the heads kernel follows and the policy Dense is always fp32.  About
      *   16/3 of the split mode's MFMA time: for match play, gating and numerics checks, not for
      *   self-play throughput.  Every row's outputs are bit-identical whatever the launch.
-     *   Stated error per config: galvanise_zero_amd/nn/tolerance.py. */
+     *   Stated error per config: galvanise_zero_amd/nn/tolerance.py.
+     *   GZ_PRECISION_BF16_LAYERED (5) / GZ_PRECISION_SPLIT_LAYERED (6): the arithmetic of
+     *   GZ_PRECISION_BF16 / GZ_PRECISION_SPLIT for the nets those modes refuse.  The trunk runs layer
+     *   by layer through GZ_PRECISION_FP32's device scratch (fp32 activations, the same
+     *   squeeze-excite, pooling and head-feature kernels), its convs on v_mfma_f32_16x16x32_bf16
+     *   with the activations converted to bf16 (split: to bf16 hi + lo, three MFMAs per product) as
+     *   they are staged into the LDS; the weight image is the fused mode's, byte for byte.  No
+     *   LDS-image limit: every board up to 19 x 19 with F <= 256 at any depth, v1 and v2 with up to
+     *   128 squeeze-excite units, every value head.  The heads run as after a single-image fused
+     *   trunk (policy_gemm_kernel for policies of >= 512 moves, then the fp32 heads kernel).  Slower
+     *   than the fused modes where those run (the activations cross HBM between layers), so
+     *   opt-in; every row's outputs are bit-identical whatever the launch. */
     int precision;
     /* v2 (pre-activation) trunk, model.py:78-151 (the reference's features=True templates and its
      * non-legacy model files); all zero = v1. */
@@ -82,6 +93,8 @@ typedef struct gz_net_desc {
 #define GZ_PRECISION_BF16 1
 #define GZ_PRECISION_SPLIT 3
 #define GZ_PRECISION_FP32 4
+#define GZ_PRECISION_BF16_LAYERED 5
+#define GZ_PRECISION_SPLIT_LAYERED 6
 
 typedef struct gz_net gz_net;
 
@@ -153,18 +166,18 @@ int gz_net_set_output_logits(gz_net* net, int on);
 float gz_net_last_kernel_ms(const gz_net* net);
 
 /* Launches of at least this many rows run the two-boards-per-workgroup trunk variant, smaller ones
- * the one-board variant (both compute every row identically).  GZ_PRECISION_FP32 has one conv
- * kernel for every launch size: 1 << 30, as for geometries with a single variant. */
+ * the one-board variant (both compute every row identically).  GZ_PRECISION_FP32 and the layered
+ * modes have one conv kernel for every launch size: 1 << 30, as for geometries with a single variant. */
 int gz_net_large_min_rows(const gz_net* net);
 
 /* The trunk kernel of launches below (large = 0) / from (large = 1) gz_net_large_min_rows rows, as
- * rocprofv3 names it (diagnostics: the bench reports its roofline per kernel).  GZ_PRECISION_FP32:
- * the conv kernel, for both. */
+ * rocprofv3 names it (diagnostics: the bench reports its roofline per kernel).  GZ_PRECISION_FP32
+ * and the layered modes: the conv kernel, for both. */
 const char* gz_net_kernel_name(const gz_net* net, int large);
 
 /* Rows one full wave of workgroups of the large variant covers (boards per workgroup x 256 CUs,
  * one trunk workgroup per CU): the native runner launches multiples of it beyond one wave.
- * GZ_PRECISION_FP32: the rows whose conv grid (128 board positions x 64 / 128 filters per
+ * GZ_PRECISION_FP32 and the layered modes: the rows whose conv grid (128 board positions x 64 / 128 filters per
  * workgroup) is one workgroup per CU. */
 int gz_net_wave_rows(const gz_net* net);
 
@@ -180,7 +193,8 @@ const char* gz_nn_last_error(void);
 /* Diagnostics: with GZ_KERNEL_STAMPS set in the environment, gz_net_forward records per-workgroup
  * s_memtime stamps at phase boundaries; out8[0] = workgroups averaged, out8[1..4] = their mean
  * cycles of (input + initial conv, residual trunk, head 1x1 convs + features, fused dense heads)
- * in the last call.  GZ_PRECISION_FP32 (many launches per forward) has no stamps: an error. */
+ * in the last call.  GZ_PRECISION_FP32 and the layered modes (many launches per forward) have no
+ * stamps: an error. */
 int gz_net_stamp_avg(const gz_net* net, double* out8);
 
 /* ---- native self-play driver (runner.hip) ----------------------------------------------------
