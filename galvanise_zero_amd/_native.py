@@ -67,6 +67,7 @@ GZ_PRECISION_SPLIT = 3
 GZ_PRECISION_FP32 = 4
 GZ_PRECISION_BF16_LAYERED = 5
 GZ_PRECISION_SPLIT_LAYERED = 6
+GZ_PRECISION_F16X3_LAYERED = 7
 # "bf16x3" (alias "split"): each fp32 operand as bf16 hi + lo, three MFMAs per product, ~16
 # significant bits per operand -- fp32-CLASS, not IEEE fp32: on the headline cfg2 batch its error
 # against the float64 oracle is ~35x an IEEE fp32 forward's (nn/tolerance.py).  "fp32" is the
@@ -76,18 +77,24 @@ GZ_PRECISION_SPLIT_LAYERED = 6
 # "bf16-layered" / "bf16x3-layered": the arithmetic of "bf16" / "bf16x3" for the nets those refuse
 # (more than 128 filters on a board above 13 x 13, more residual blocks than their LDS image leaves
 # room for): the trunk layer by layer through HBM like fp32-ieee's, its convs on the bf16 MFMA.
+# "fp16x3-layered": fp32-class accuracy at the bf16 MFMA's rate on the same layer-by-layer trunk --
+# each operand an fp16 hi part plus an fp16 lo part scaled by 2^11 (22 significand bits), three
+# v_mfma_f32_16x16x32_f16 per product, one power-of-two exponent per board and conv input to stay
+# within fp16's range; heads as in fp32-ieee.  Conv weights must fit fp16 after the BN fold.
 PRECISIONS = {"bf16": GZ_PRECISION_BF16, "bf16x3": GZ_PRECISION_SPLIT, "split": GZ_PRECISION_SPLIT,
               "fp32": GZ_PRECISION_SPLIT, "fp32-ieee": GZ_PRECISION_FP32,
-              "bf16-layered": GZ_PRECISION_BF16_LAYERED, "bf16x3-layered": GZ_PRECISION_SPLIT_LAYERED}
+              "bf16-layered": GZ_PRECISION_BF16_LAYERED, "bf16x3-layered": GZ_PRECISION_SPLIT_LAYERED,
+              "fp16x3-layered": GZ_PRECISION_F16X3_LAYERED}
 _CANONICAL = {GZ_PRECISION_BF16: "bf16", GZ_PRECISION_SPLIT: "bf16x3", GZ_PRECISION_FP32: "fp32-ieee",
-              GZ_PRECISION_BF16_LAYERED: "bf16-layered", GZ_PRECISION_SPLIT_LAYERED: "bf16x3-layered"}
+              GZ_PRECISION_BF16_LAYERED: "bf16-layered", GZ_PRECISION_SPLIT_LAYERED: "bf16x3-layered",
+              GZ_PRECISION_F16X3_LAYERED: "fp16x3-layered"}
 
 
 def canonical_precision(precision):
-    """The arithmetic mode's canonical name ("bf16", "bf16x3", "fp32-ieee", "bf16-layered" or
-    "bf16x3-layered"); "split" and the deprecated "fp32" name bf16x3."""
+    """The arithmetic mode's canonical name ("bf16", "bf16x3", "fp32-ieee", "bf16-layered",
+    "bf16x3-layered" or "fp16x3-layered"); "split" and the deprecated "fp32" name bf16x3."""
     if precision not in PRECISIONS:
-        raise ValueError("precision %r: one of bf16, bf16x3 (alias split), fp32-ieee, bf16-layered, bf16x3-layered "
+        raise ValueError("precision %r: one of bf16, bf16x3 (alias split), fp32-ieee, bf16-layered, bf16x3-layered, fp16x3-layered "
                          "(fp32 is a deprecated alias of bf16x3)" % (precision,))
     if precision == "fp32":
         import warnings
@@ -190,7 +197,11 @@ class HipNet(object):
     bf16x3: for match play, gating and numerics checks), or "bf16-layered" / "bf16x3-layered"
     (GZ_PRECISION_BF16_LAYERED / _SPLIT_LAYERED: bf16's / bf16x3's arithmetic and weight image on
     fp32-ieee's layer-by-layer trunk, for the nets the fused modes refuse -- F > 128 above 13 x 13,
-    or deeper than their LDS image allows; slower than the fused modes where those run).
+    or deeper than their LDS image allows; slower than the fused modes where those run), or
+    "fp16x3-layered" (GZ_PRECISION_F16X3_LAYERED: fp16 hi + scaled-lo operands on the f16 MFMA with
+    a per-board exponent, on the same layer-by-layer trunk and geometries -- fp32-class accuracy at
+    a fraction of fp32-ieee's time: the first choice for match play, gating and numerics checks;
+    set_weights refuses a blob whose BN-folded conv weights do not fit fp16).
     "fp32" is a deprecated alias of "bf16x3";
     self.precision holds the canonical name."""
 

@@ -126,7 +126,7 @@ namespace gzfp32 {
 // One conv launch of the layer loop
 struct ConvArgs {
     const float* x;        // [ncols][cinp]
-    const void* w;         // fp32: wfrag_index order; layered: the bf16 image (hi parts, or hi | lo fragments)
+    const void* w;         // fp32: wfrag_index order; layered: the bf16 / fp16 image (hi parts, or hi | lo fragments)
     const float* bias;     // [FP]
     const float* skip;     // [ncols][FP] added before the activation, or nullptr (may alias out)
     float* out;            // [ncols][FP]
@@ -136,7 +136,7 @@ struct ConvArgs {
     int ncols, cinp, taps, FP, H, W, npos, act, leaky;
     // the layered modes (layered_forward.h)
     const void* wlo;       // the initial conv's lo image (parts == 3)
-    int parts;             // 1: bf16, 3: split
+    int parts;             // 1: bf16, 3: split, gzlayered::kF16Parts: fp16x3
     int w0_layout;         // w is the initial conv's [K0 / 32][FP][32] image (taps == 1, cinp == K0)
 };
 
@@ -152,8 +152,11 @@ struct Forward {
     int scratch_rows = 0;
     size_t scratch_bytes = 0;
     // The layered modes (layered_forward.h) run the same layer loop with their own conv and input
-    // gather: parts = 1 (bf16) or 3 (split), the weights kp.w0 / kp.w0lo / kp.wres; 0: the fp32 conv
+    // gather: parts = 1 (bf16) or 3 (split), the weights kp.w0 / kp.w0lo / kp.wres; 0: the fp32 conv.
+    // parts = gzlayered::kF16Parts: the fp16x3 conv over the fp16 hi | lo image, each conv behind the
+    // per-board exponents of its input in bexp (scratch_rows ints, the net's own buffer)
     int parts = 0;
+    int* bexp = nullptr;
 };
 
 // Queues the trunk of kp.n rows on `stream`: gather, convs, squeeze-excite, the head features into

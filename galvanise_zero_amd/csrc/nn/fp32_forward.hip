@@ -290,10 +290,11 @@ const char* forward(const KParams& kp, const Forward& f, hipStream_t st) {
     // every size the kernels rely on, before anything is launched
     if (kp.n < 1) return nullptr;
     const bool layered = f.parts != 0;   // the conv and the input gather of layered_forward.h
-    if (layered && f.parts != 1 && f.parts != 3) return "fp32 forward: bad part count";
-    if (layered ? (!kp.w0 || (f.parts == 3 && !kp.w0lo) || (B > 0 && !kp.wres)) : (!f.w0 || (B > 0 && !f.wres)))
+    const bool f16 = f.parts == gzlayered::kF16Parts;   // conv_f16_kernel behind board_exp_kernel
+    if (layered && f.parts != 1 && f.parts != 3 && !f16) return "fp32 forward: bad part count";
+    if (layered ? (!kp.w0 || (f.parts != 1 && !kp.w0lo) || (B > 0 && !kp.wres)) : (!f.w0 || (B > 0 && !f.wres)))
         return "fp32 forward: missing weights";
-    if (!f.scratch || !kp.feat) return "fp32 forward: missing buffer";
+    if (!f.scratch || !kp.feat || (f16 && !f.bexp)) return "fp32 forward: missing buffer";
     if (kp.H < 1 || kp.W < 1 || kp.H > kMaxBoardSide || kp.W > kMaxBoardSide || npos != kp.H * kp.W)
         return "fp32 forward: board out of range";
     if (padded_filters(FP) != FP || CP != (layered ? kp.K0 : pad16(kp.C)) || FP > 256 || kp.S > kMaxSE)
@@ -330,6 +331,7 @@ const char* forward(const KParams& kp, const Forward& f, hipStream_t st) {
             a.out2 = out2;
             a.psc = out2 ? kp.pre + (size_t)(2 * pre_blk) * FP : nullptr;
             a.psh = out2 ? kp.pre + (size_t)(2 * pre_blk + 1) * FP : nullptr;
+            if (f16) return gzlayered::launch_conv_f16(a, f.bexp, st);
             return layered ? gzlayered::launch_conv(a, st) : launch_conv(a, st);
         };
         const char* e;

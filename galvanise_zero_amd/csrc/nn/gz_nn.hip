@@ -83,8 +83,11 @@ struct gz_net : PackSpec {         // d, fpad, p2, K0, cp, fp32, gemm_heads: wha
     const float* wresf = nullptr;
     std::map<hipStream_t, std::pair<char*, int>> fscr;   // scratch and the rows it holds
     // GZ_PRECISION_BF16_LAYERED / _SPLIT_LAYERED (layered_forward.h): the same layer-wise trunk and scratch
-    // with the bf16 conv over the fused modes' weight image; 1 (bf16) or 3 (split) parts, 0: another mode
+    // with the bf16 conv over the fused modes' weight image; 1 (bf16) or 3 (split) parts, 0: another mode.
+    // GZ_PRECISION_F16X3_LAYERED: gzlayered::kF16Parts (PackSpec::f16 set), the fp16 hi | lo image and the
+    // per-board exponents of each conv's input, one buffer of as many ints as scratch rows per stream
     int layered = 0;
+    std::map<hipStream_t, int*> bexp;
     int in_width() const { return layered ? K0 : cp; }   // input channels of the initial conv's launch
 };
 
@@ -135,7 +138,8 @@ extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
     }
     const int precision = d.precision == 0 ? GZ_PRECISION_BF16 : d.precision;
     const bool fp32 = precision == GZ_PRECISION_FP32;
-    const int layered = precision == GZ_PRECISION_BF16_LAYERED ? 1 : precision == GZ_PRECISION_SPLIT_LAYERED ? 3 : 0;
+    const int layered = precision == GZ_PRECISION_BF16_LAYERED ? 1 : precision == GZ_PRECISION_SPLIT_LAYERED ? 3 :
+                        precision == GZ_PRECISION_F16X3_LAYERED ? gzlayered::kF16Parts : 0;
     const bool layerwise = fp32 || layered;   // the trunk layer by layer through HBM: no LDS-image limit
     if (precision != GZ_PRECISION_BF16 && precision != GZ_PRECISION_SPLIT && !layerwise) { fail("unknown precision"); return nullptr; }
     int vs = kSmallVariant, vl = kLargeVariant, min_large = kLargeMinRows;
@@ -255,8 +259,8 @@ extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
     // layers run as one MFMA GEMM per launch (policy_gemm_kernel) instead of heads_kernel's
     // per-4-board fp32 loop (amazons P = 3041: 12 % of the forward).  Every launch of such a net
     // takes this path, so results stay batch-invariant.
-    // (fp32-ieee: the policy Dense stays fp32 on the VALU)
-    net->gemm_heads = !fp32 && !net->small.fused_heads && !net->large.fused_heads && maxP >= 512 &&
+    // (fp32-ieee, fp16x3-layered: the policy Dense stays fp32 on the VALU)
+    net->gemm_heads = !fp32 && !net->f16 && !net->small.fused_heads && !net->large.fused_heads && maxP >= 512 &&
                       getenv("GZ_NO_GEMM_HEADS") == nullptr;
     KParams& kp = net->kp;
     kp.C = d.input_channels;
@@ -315,7 +319,7 @@ extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
         }
     }
     if (net->heads_smem > 64 * 1024 &&
-        hipFuncSetAttribute(fp32 ? (const void*)&heads_kernel_blocked : (const void*)&heads_kernel,
+        hipFuncSetAttribute(fp32 || net->f16 ? (const void*)&heads_kernel_blocked : (const void*)&heads_kernel,
                             hipFuncAttributeMaxDynamicSharedMemorySize, net->heads_smem) != hipSuccess) {
         fail("cannot raise dynamic LDS limit (heads)");
         delete net;
@@ -334,6 +338,7 @@ extern "C" void gz_net_destroy(gz_net* net) {
     for (auto& f : net->resid) (void)hipFree(f.second.first);
     for (auto& f : net->glog) (void)hipFree(f.second.first);
     for (auto& f : net->fscr) (void)hipFree(f.second.first);
+    for (auto& f : net->bexp) (void)hipFree(f.second);
     if (net->ev0) (void)hipEventDestroy(net->ev0);
     if (net->ev1) (void)hipEventDestroy(net->ev1);
     if (net->stream) (void)hipStreamDestroy(net->stream);
@@ -425,7 +430,15 @@ extern "C" int gz_net_set_weights(gz_net* net, const float* blob, size_t count) 
     if (check_count(net, blob, count)) return -1;
     const ImageLayout I = image_layout(*net);
     std::vector<char> img(I.total, 0);
-    pack_image_host(job_list(*net, blob_plan(net->d), I), blob, RawImage{img.data()});
+    const JobList J = job_list(*net, blob_plan(net->d), I);
+    if (net->f16) {   // a weight fp16 cannot hold would turn the conv's outputs non-finite
+        const int conv = f16_range_check(J, blob);
+        if (conv >= 0)
+            return fail((conv == 0 ? std::string("initial conv") : "trunk conv " + std::to_string(conv - 1) + " (residual block " +
+                                                                     std::to_string((conv - 1) / 2) + ")") +
+                        ": a BN-folded weight is outside fp16's finite range (|w| >= 65,520): fp16x3-layered cannot hold it");
+    }
+    pack_image_host(J, blob, RawImage{img.data()});
     HIPCHK(hipSetDevice(net->device));
     char* m = nullptr;
     HIPCHK(hipMalloc((void**)&m, I.total));
@@ -438,6 +451,9 @@ extern "C" int gz_net_set_weights(gz_net* net, const float* blob, size_t count) 
 
 // The same jobs on the device (generation roll: the blob arrives in HBM by an RCCL broadcast), the
 // element functions computing every value with the host's operations and rounding.
+// fp16x3-layered: the blob's BN-folded conv weights must lie within fp16's finite range (a
+// precondition here, checked by gz_net_set_weights only): a larger one becomes an infinite hi part
+// and non-finite outputs; nothing is clamped.
 extern "C" int gz_net_set_weights_device(gz_net* net, const float* d_blob, size_t count) {
     if (check_count(net, d_blob, count)) return -1;
     if (getenv("GZ_HOST_WEIGHT_ROLL")) {   // diagnostics: the round-trip path (D2H, host fold / pack, H2D)
@@ -566,7 +582,7 @@ static int launch_segments(gz_net* net, hipStream_t stream, const gz_segment* se
     }
     if (net->fp32 || net->layered) {
         // the layer-wise trunk (fp32_forward.hip), then the heads: fp32-ieee's kernel with blocked Dense
-        // sums, the layered modes' as after a single-image bf16 / bf16x3 trunk
+        // sums (fp16x3-layered's too), the bf16 layered modes' as after a single-image bf16 / bf16x3 trunk
         gzfp32::Forward f;
         f.parts = net->layered;
         if (net->fp32) {
@@ -590,7 +606,14 @@ static int launch_segments(gz_net* net, hipStream_t stream, const gz_segment* se
                 const int cap = std::max(need, std::min(net->chunk_rows, 64));
                 HIPCHK(hipMalloc((void**)&s.first, gzfp32::scratch_layout(cap, kp.npos, f.CP, f.FP).total));
                 s.second = cap;
+                if (net->f16) {   // (the sync above, if any, covers the launches that read the old one)
+                    int*& be = net->bexp[stream];
+                    if (be) HIPCHK(hipFree(be));
+                    be = nullptr;
+                    HIPCHK(hipMalloc((void**)&be, (size_t)cap * sizeof(int)));
+                }
             }
+            if (net->f16) f.bexp = net->bexp[stream];
             f.scratch = s.first;
             f.scratch_rows = s.second;
             f.scratch_bytes = gzfp32::scratch_layout(s.second, kp.npos, f.CP, f.FP).total;
@@ -605,7 +628,7 @@ static int launch_segments(gz_net* net, hipStream_t stream, const gz_segment* se
             HIPCHK(hipLaunchKernel((const void*)&policy_gemm_kernel, dim3((n + 63) / 64, (maxjt + 7) / 8, kp.R), dim3(256),
                                    hargs, 0, stream));
         }
-        HIPCHK(hipLaunchKernel(net->fp32 ? (const void*)&heads_kernel_blocked : (const void*)&heads_kernel,
+        HIPCHK(hipLaunchKernel(net->fp32 || net->f16 ? (const void*)&heads_kernel_blocked : (const void*)&heads_kernel,
                                dim3((n + kHeadBoards - 1) / kHeadBoards), dim3(256), hargs, net->heads_smem, stream));
         return 0;
     }

@@ -21,6 +21,22 @@
 //
 // The initial conv runs as a 1-tap conv over an im2col image [ncols][K0] (k = tap C + c, zero off
 // the board and in the padding to K0), reading the w0 image by w0_frag_index.
+//
+// GZ_PRECISION_F16X3_LAYERED ("fp16x3-layered", Forward::parts == kF16Parts) is the same path with
+// conv_f16_kernel<CT> on v_mfma_f32_16x16x32_f16: the split conv's tiling, LDS rows, fragment
+// addresses and image offsets (any 2-byte element), with fp16 parts and a per-board exponent.  For a
+// conv with BN-folded weights w and input x, e_b the exponent of the column's board (board_exponent
+// of the largest |x| among the board's npos x cinp inputs, written to bexp[row] by board_exp_kernel
+// in front of the conv):
+//   x^   = x 2^-e_b                       (exact: the board's largest |x^| lies in [2^14, 2^15))
+//   x_hi = f16(x^)      x_lo = f16((x^ - x_hi) 2^11)       round to nearest even
+//   w_hi = f16(w)       w_lo = f16((w  - w_hi) 2^11)       (weight_image.h f2h / h_lo_of)
+//   main += w_hi x_hi ;  corr += w_hi x_lo ;  corr += w_lo x_hi     per k-step, two fp32 accumulators
+//   out  = (main + corr 2^-11) 2^e_b      then bias / skip / activation / pre-activation as above
+// lo lo is dropped.  The lo parts are scaled so that they stay clear of fp16's subnormals, and summed
+// apart so that the scale comes off once.  A 3x3 neighbourhood never leaves its board, so e_b factors
+// out of every column; it depends on the board's own data only, so a row's outputs stay independent
+// of the launch.  A board with an infinity or a NaN gets e_b = 0 and non-finite outputs.
 #pragma once
 
 #include "fp32_forward.h"
@@ -33,8 +49,10 @@ using gzfp32::kWaveTiles;
 
 constexpr int kStep = 32;   // input channels per MFMA (v_mfma_f32_16x16x32_bf16)
 
-// bf16 parts per operand of precision P (1 or 3) = weight_image.h's PackSpec.p2
-GZF_HD inline int operand_parts(int P) { return P == 3 ? 2 : 1; }
+constexpr int kF16Parts = 16;   // Forward::parts / P of the fp16x3 conv (1: bf16, 3: bf16 split)
+
+// 2-byte parts per operand of precision P (1, 3 or kF16Parts) = weight_image.h's PackSpec.p2
+GZF_HD inline int operand_parts(int P) { return P == 3 || P == kF16Parts ? 2 : 1; }
 
 // ---- LDS image of one (tile, chunk) ------------------------------------------------------------
 // Row stride in bytes: 160 (P = 1: 128 of hi + 32) or 288 (P = 3: 128 hi + 128 lo + 32), i.e. 10 or
@@ -67,6 +85,24 @@ GZF_HD inline size_t w0_frag_index(int kc, int cot, int li, int g, int FP) {
     return (((size_t)kc * FP + 16 * cot + li) * kStep) + 8 * g;
 }
 
+// ---- fp16x3: the per-board exponent -------------------------------------------------------------
+// e_b from the largest bit pattern of |x| (as unsigned: the order of the magnitudes) among a board's
+// inputs: floor(log2(max |x|)) - 14, subnormals included; 0 for an all-zero board and for one holding
+// an infinity or a NaN (whose pattern is the largest), which then reaches the outputs as it is.
+GZF_HD inline int board_exponent(unsigned maxbits) {
+    if (maxbits == 0u || maxbits >= 0x7f800000u) return 0;
+    int fl;
+    if (maxbits >= 0x00800000u) {
+        fl = (int)(maxbits >> 23) - 127;
+    } else {
+        int top = 22;   // the subnormal's highest set bit
+        while (!((maxbits >> top) & 1u)) --top;
+        fl = top - 149;
+    }
+    return fl - 14;
+}
+constexpr float kF16LoInv = 1.f / 2048.f;   // 2^-11 (gzw::kF16LoScale's inverse)
+
 // ---- the im2col image of the initial conv --------------------------------------------------------
 // what element k of a column at board position (y, x) reads: plane *c at (y + *dy, x + *dx); false
 // for the padding k >= taps C.  taps = 9 (3x3) or 1 (1x1).
@@ -91,6 +127,9 @@ const char* launch_conv(const gzfp32::ConvArgs& a, hipStream_t st);
 void launch_im2col(const gznn::KParams& kp, float* in, int row0, int rows, hipStream_t st);
 // the conv kernel of a net with FP padded filters and precision P, as rocprofv3 names it
 const char* conv_kernel_name(int FP, int P);
+// fp16x3: board_exp_kernel over the conv's input (a.ncols / a.npos boards of a.npos x a.cinp values)
+// into bexp, then conv_f16_kernel; a.w / a.wlo the fp16 images, a.parts == kF16Parts
+const char* launch_conv_f16(const gzfp32::ConvArgs& a, int* bexp, hipStream_t st);
 
 }  // namespace gzlayered
 #endif

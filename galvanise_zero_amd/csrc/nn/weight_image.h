@@ -42,6 +42,7 @@ struct PackSpec {
     int cp = 0;                // input planes padded to 16 (fp32-ieee)
     bool fp32 = false;         // GZ_PRECISION_FP32: fp32 conv images (fp32_forward.h) instead of the bf16 ones
     bool gemm_heads = false;   // policy heads by policy_gemm_kernel: its A fragments follow the image
+    bool f16 = false;          // GZ_PRECISION_F16X3_LAYERED: the conv images' parts are fp16 hi | fp16 lo scaled by 2^11
 };
 
 inline int initial_kernel(const gz_net_desc& d) {
@@ -49,12 +50,14 @@ inline int initial_kernel(const gz_net_desc& d) {
 }
 // The spec of desc d in arithmetic mode `precision` (gz_net_desc.precision, not 0) with fpad padded
 // filters.  The layered modes pack the image of the fused mode with the same operand parts: the two
-// specs are equal, so are the images.
+// specs are equal, so are the images.  "fp16x3-layered" packs the split image's layout (p2 = 2) with
+// fp16 parts (f2h / h_lo_of in place of f2bf / lo_of).
 inline PackSpec pack_spec(const gz_net_desc& d, int precision, int fpad, bool gemm_heads) {
     PackSpec s;
     s.d = d;
     s.fpad = fpad;
-    s.p2 = (precision == GZ_PRECISION_SPLIT || precision == GZ_PRECISION_SPLIT_LAYERED) ? 2 : 1;
+    s.f16 = precision == GZ_PRECISION_F16X3_LAYERED;
+    s.p2 = (precision == GZ_PRECISION_SPLIT || precision == GZ_PRECISION_SPLIT_LAYERED || s.f16) ? 2 : 1;
     s.K0 = ((initial_kernel(d) * initial_kernel(d) * d.input_channels + 31) / 32) * 32;
     s.cp = (d.input_channels + 15) & ~15;
     s.fp32 = precision == GZ_PRECISION_FP32;
@@ -234,6 +237,7 @@ enum JobKind {
 struct Job {
     int kind = 0, rows = 1, cols = 0;
     int F = 0, FP = 0, cin = 0, cinp = 0, P2 = 1;   // convs: model / padded output and input channels
+    int f16 = 0;                                    // convs: fp16 hi | scaled lo parts instead of bf16 ones
     int ss = 1, ds = 1;
     size_t src = 0, sc = kNone, bi = kNone;
     size_t dst = 0, dst_lo = kNone, dst_bias = kNone;
@@ -258,7 +262,7 @@ inline JobList job_list(const PackSpec& s, const BlobPlan& P, const ImageLayout&
     auto conv = [&](int kind, size_t w, const BNRef& bn, int taps, int cin, int cinp, size_t dst, size_t dst_lo, size_t dst_bias) {
         Job j;
         j.kind = kind; j.rows = taps * cin; j.cols = F;
-        j.F = F; j.FP = FP; j.cin = cin; j.cinp = cinp; j.P2 = s.p2;
+        j.F = F; j.FP = FP; j.cin = cin; j.cinp = cinp; j.P2 = s.p2; j.f16 = s.f16 ? 1 : 0;
         j.src = w; j.sc = bn.scale(); j.bi = bn.bias();
         j.dst = dst; j.dst_lo = dst_lo; j.dst_bias = dst_bias;
         J.packs.push_back(j);
@@ -359,6 +363,36 @@ GZW_HD inline uint16_t lo_of(float v) {
     return f2bf(f_sub(v, __builtin_bit_cast(float, (uint32_t)f2bf(v) << 16)));
 }
 
+// fp16 (IEEE binary16), round to nearest even: subnormals kept, 65,520 and above to infinity
+GZW_HD inline uint16_t f2h(float f) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, f), a = u & 0x7fffffffu;
+    const uint16_t sign = (uint16_t)((u >> 16) & 0x8000u);
+    if (a > 0x7f800000u) return (uint16_t)(sign | 0x7e00u);   // quiet NaN
+    if (a >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);  // rounds to 2^16 or more: infinity
+    if (a < 0x33000001u) return sign;                         // at most 2^-25: zero (the tie goes to even)
+    const int e = (int)(a >> 23) - 127;                       // -25 .. 15
+    const uint32_t m = (a & 0x007fffffu) | 0x00800000u;       // 24 bits
+    // the result's unit in the last place is 2^(e - 10), or 2^-24 below the normals: drop `sh` bits
+    const int sh = e >= -14 ? 13 : 13 + (-14 - e);            // 13 .. 24
+    const uint32_t keep = m >> sh, rest = m & ((1u << sh) - 1u), half = 1u << (sh - 1);
+    const uint32_t r = keep + ((rest > half || (rest == half && (keep & 1u))) ? 1u : 0u);
+    // normals: r carries the hidden bit at 2^10, a carry out of the significand raises the exponent
+    // (subnormals: the exponent field is 0 and r, up to 2^10, is the field or the smallest normal)
+    return (uint16_t)(sign | (e >= -14 ? (uint32_t)(e + 14) * 1024u + r : r));
+}
+GZW_HD inline float h2f(uint16_t h) {
+    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 1023u;
+    if (e == 31u) return __builtin_bit_cast(float, sign | 0x7f800000u | (m << 13));
+    if (e) return __builtin_bit_cast(float, sign | ((e + 112u) << 23) | (m << 13));
+    // subnormal: m 2^-24, exact in fp32 (the product of an integer below 2^10 and a power of two)
+    const float v = (float)m * 5.9604644775390625e-8f;
+    return sign ? -v : v;
+}
+// fp16x3: x = hi + lo 2^-11, hi = f16(x), lo = f16((x - hi) 2^11) -- the subtraction and the scaling are
+// exact in fp32; the scaled lo part stays clear of fp16's subnormals (Ootomo and Yokota's scheme)
+constexpr float kF16LoScale = 2048.f;
+GZW_HD inline uint16_t h_lo_of(float v) { return f2h(f_mul(f_sub(v, h2f(f2h(v))), kF16LoScale)); }
+
 // Element offset (within one trunk conv's image) of weight [co][ci] of tap `tap`, hi part; the lo
 // part (split precision) sits 512 elements (1 KB) further.  A k-step (tap, 32 input channels) is
 // FP/16 blocks of 16 output channels; block = P2 fragments of 1 KB, each in MFMA A-fragment lane
@@ -393,14 +427,14 @@ GZW_HD inline void fold_element(const BNRef& b, int i, const float* blob, float*
 template <class Img>
 GZW_HD inline void w0_element(const Img& img, const Job& j, int k, int co, float v) {
     const size_t o = (((size_t)(k / 32) * j.FP + co) * 32 + (k % 32)) * 2;
-    img.put16(j.dst + o, f2bf(v));
-    if (j.dst_lo != kNone) img.put16(j.dst_lo + o, lo_of(v));
+    img.put16(j.dst + o, j.f16 ? f2h(v) : f2bf(v));
+    if (j.dst_lo != kNone) img.put16(j.dst_lo + o, j.f16 ? h_lo_of(v) : lo_of(v));
 }
 template <class Img>
 GZW_HD inline void trunk_conv_element(const Img& img, const Job& j, int tap, int co, int ci, float v) {
     const size_t o = j.dst + wres_index(tap, co, ci, j.FP, j.P2) * 2;
-    img.put16(o, f2bf(v));
-    if (j.P2 == 2) img.put16(o + 512 * 2, lo_of(v));
+    img.put16(o, j.f16 ? f2h(v) : f2bf(v));
+    if (j.P2 == 2) img.put16(o + 512 * 2, j.f16 ? h_lo_of(v) : lo_of(v));
 }
 // (the product is one fp32 multiply, rounded once)
 template <class Img>
@@ -459,6 +493,26 @@ inline void pack_image_host(const JobList& J, const float* blob, const Img& img)
         case kPackF32: run(std::integral_constant<int, kPackF32>(), j); break;
         default: run(j.kind, j);
         }
+}
+
+// fp16x3-layered: the first conv with a folded weight that fp16 cannot hold (its hi part would be
+// infinite) -- 0 the initial conv, c + 1 trunk conv c -- or -1 when every weight fits
+GZW_HD inline bool f16_holds(const Job& j, int r, int c, const float* blob, const float* fold) {
+    return (f2h(f_mul(blob[j.src + (size_t)r * j.F + c], fold[j.sc + c])) & 0x7fffu) < 0x7c00u;
+}
+inline int f16_range_check(const JobList& J, const float* blob) {
+    std::vector<float> fold((size_t)J.fold_floats);
+    for (const BNRef& b : J.folds)
+        for (int i = 0; i < b.n; ++i) fold_element(b, i, blob, fold.data());
+    int conv = 0;
+    for (const Job& j : J.packs) {
+        if (j.kind != kPackW0 && j.kind != kPackTrunk) continue;
+        for (int r = 0; r < j.rows; ++r)
+            for (int c = 0; c < j.cols; ++c)
+                if (!f16_holds(j, r, c, blob, fold.data())) return conv;
+        ++conv;
+    }
+    return -1;
 }
 
 }  // namespace gzw

@@ -15,7 +15,8 @@ from .weights import from_blob, random_weights, to_blob
 
 class Manager(object):
     """precision: the arithmetic mode of the networks it builds (a _native.PRECISIONS name, e.g.
-    "bf16x3-layered" for nets the fused modes refuse); each building method takes its own too."""
+    "bf16x3-layered" for nets the fused modes refuse, "fp16x3-layered" for fp32-class match play and
+    gating); each building method takes its own too."""
 
     def __init__(self, data_path=None, device=0, precision="bf16"):
         self.data_path = data_path or os.environ.get("GGPZERO_PATH", ".")

@@ -55,6 +55,15 @@ at most 2.91e-5 (both on the 13 x 13 v1 net of 14 x 256, 2 rows; 2.8-7.2e-6 on t
 0.76-1.01 x the fused bf16x3's on the same rows); bf16-layered max 1.04e-3 (6 x 9 legacy net, 7 rows), equal to
 the fused bf16's on the same rows to the printed digits on every net both run.
 
+"fp16x3-layered" (GZ_PRECISION_F16X3_LAYERED: the layered trunk with each operand as fp16 hi + fp16
+lo scaled by 2^11 -- 22 significand bits against bf16x3's 16 and fp32's 24 --, three f16 MFMAs per
+product into two fp32 accumulators, one power-of-two exponent per board and conv input against
+fp16's range, the heads fp32-ieee's) has no constants here: tests/test_nn_fp16x3_gpu.py bounds its
+relative logit error by the two neighbouring modes' on the same weights and rows -- at most 4 x
+fp32-ieee's (two significand bits fewer per operand) and at most a quarter of bf16x3-layered's (six
+bits more) -- and its probabilities by DAMPED_TOLERANCE.  The errors measured on MI355X are in
+profiles/fp16x3_gpu_tests.txt and DESIGN 3.1.
+
 The north-star tolerance per config, then:
   cfg2, cfg3   the probability bounds below (max / mean / KL), on the bench's weights
   cfg4, cfg5   the relative logits bound below on the bench's (saturating) weights, and in probability

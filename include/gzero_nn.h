@@ -75,7 +75,19 @@ typedef struct gz_net_desc {
      *   128 squeeze-excite units, every value head.  The heads run as after a single-image fused
      *   trunk (policy_gemm_kernel for policies of >= 512 moves, then the fp32 heads kernel).  Slower
      *   than the fused modes where those run (the activations cross HBM between layers), so
-     *   opt-in; every row's outputs are bit-identical whatever the launch. */
+     *   opt-in; every row's outputs are bit-identical whatever the launch.
+     *   GZ_PRECISION_F16X3_LAYERED (7): fp32-class arithmetic at the bf16 MFMA's rate, on the same
+     *   layer-by-layer trunk.  Each operand is an fp16 hi part plus an fp16 lo part scaled by 2^11
+     *   (22 significand bits against fp32's 24), three v_mfma_f32_16x16x32_f16 per product (hi hi
+     *   into one fp32 accumulator, hi lo + lo hi into a second, joined as main + corr 2^-11).  fp16's
+     *   range is kept by one power-of-two exponent per board and conv input (board_exp_kernel: the
+     *   board's largest |x| scaled into [2^14, 2^15)), a function of the board's own data, so every
+     *   row's outputs stay bit-identical whatever the launch.  Geometry limits as modes 5 / 6; the
+     *   heads run as in GZ_PRECISION_FP32 (policy Dense fp32 on the VALU).  A BN-folded conv weight
+     *   of 65,520 or more in magnitude does not fit fp16: gz_net_set_weights refuses such a blob
+     *   naming the conv; gz_net_set_weights_device requires the caller to rule it out (the weight
+     *   becomes infinite and the outputs non-finite, nothing is clamped).  For match play, gating
+     *   and numerics checks; GZ_PRECISION_FP32 stays the IEEE reference. */
     int precision;
     /* v2 (pre-activation) trunk, model.py:78-151 (the reference's features=True templates and its
      * non-legacy model files); all zero = v1. */
@@ -95,6 +107,7 @@ typedef struct gz_net_desc {
 #define GZ_PRECISION_FP32 4
 #define GZ_PRECISION_BF16_LAYERED 5
 #define GZ_PRECISION_SPLIT_LAYERED 6
+#define GZ_PRECISION_F16X3_LAYERED 7
 
 typedef struct gz_net gz_net;
 
