@@ -150,6 +150,9 @@ def nn_lib():
         lib.gz_net_large_min_rows.argtypes = [ctypes.c_void_p]
         lib.gz_net_wave_rows.restype = ctypes.c_int
         lib.gz_net_wave_rows.argtypes = [ctypes.c_void_p]
+        if hasattr(lib, "gz_net_workgroups_per_cu"):   # (absent from older A/B builds loaded through GZ_LIB_DIR)
+            lib.gz_net_workgroups_per_cu.restype = ctypes.c_int
+            lib.gz_net_workgroups_per_cu.argtypes = [ctypes.c_void_p]
         lib.gz_nn_last_error.restype = ctypes.c_char_p
         lib._gz_typed = True
     return lib
@@ -301,6 +304,12 @@ class HipNet(object):
     def wave_rows(self):
         """Rows of one full wave of trunk workgroups (fp32-ieee: of its conv grid), gz_net_wave_rows."""
         return self.lib.gz_net_wave_rows(self.handle)
+
+    def workgroups_per_cu(self):
+        """Workgroups of the large trunk kernel resident per CU (2: trunk_kernel_h2i), gz_net_workgroups_per_cu."""
+        if not hasattr(self.lib, "gz_net_workgroups_per_cu"):
+            return 1
+        return self.lib.gz_net_workgroups_per_cu(self.handle)
 
     def heads_fused(self):
         """True when the large trunk variant runs the dense heads itself (no heads_kernel launch)."""

@@ -192,7 +192,9 @@ __host__ __device__ constexpr int lcm_c(int a, int b) { return a / gcd_c(a, b) *
 // the same weight stream per workgroup, two waves per SIMD, 256 registers per wave); WG = 4: two
 // groups of 2 waves, a board each (NB = 1), each wave half the output channels of its board (twice
 // the 4-wave layout's co tiles, half its position tiles: half the B-fragment reads per MFMA, twice
-// the weight fragments)
+// the weight fragments); WG = 5: WG = 4's decomposition with ONE image per board, overwritten in place
+// (INPL), and a 2-stage weight ring, so a wave fits 256 registers and a workgroup half the LDS: two
+// independent workgroups per CU, whose epilogues, barriers and fixed phases overlap each other's MFMAs
 template <int F, int PTN, int NB = 1, int P = 1, int WG = 1>
 struct Geo {
     static constexpr int P2 = P == 3 ? 2 : 1;        // bf16 parts per activation in the LDS image
@@ -201,8 +203,8 @@ struct Geo {
     static constexpr int NPOS = 16 * PTN;            // position capacity (the real count is kp.npos)
     static constexpr int PT = PTN;                   // position tiles per board (MFMA N)
     static constexpr int TT = NB * PT;               // position tiles per wave (all boards)
-    static constexpr int NWV = WG == 3 ? 8 : WG == 4 ? 2 : 4;   // waves per group
-    static constexpr int NGR = WG == 2 || WG == 4 ? 2 : 1;      // wave groups per workgroup
+    static constexpr int NWV = WG == 3 ? 8 : (WG == 4 || WG == 5) ? 2 : 4;   // waves per group
+    static constexpr int NGR = WG == 2 || WG == 4 || WG == 5 ? 2 : 1;      // wave groups per workgroup
     static constexpr int CT = F / (16 * NWV);        // co tiles per wave (MFMA M)
     static constexpr int KC = F / 32;                // k-steps per tap
     static constexpr int CPR = F / 8;                // 16-byte chunks of channels per row
@@ -239,8 +241,9 @@ struct Geo {
     static constexpr int NST = 9 * KC / KS;          // ring stages per conv
     // ring depth; the two-board split kernels take exactly one tap's stages (R = KC / KS) so the
     // looped conv's body is one tap (a deeper ring made the body three taps and spilled)
-    static constexpr int R0 = (P2 == 2 && (NB == 2 || WG == 2 || WG == 4) && (KC / KS) >= 3 && NST % (KC / KS) == 0 &&
-                               (KC / KS) * KS * NFR * 4 <= (WG == 4 ? GZ_H2_RING_VGPRS : 96))
+    // (WG = 5: 256 registers per wave -- the 64-VGPR 2-stage ring of ring_depth below)
+    static constexpr int R0 = (P2 == 2 && (NB == 2 || WG == 2 || WG == 4 || WG == 5) && (KC / KS) >= 3 && NST % (KC / KS) == 0 &&
+                               (KC / KS) * KS * NFR * 4 <= (WG == 4 ? GZ_H2_RING_VGPRS : WG == 5 ? 64 : 96))
                                   ? KC / KS
                                   : ring_depth(NST, KS, NFR, CT >= 4 ? 64 : 96);
     // Single-image mode: when two ping-pong images (+ bias table) do not fit the 160 KB of LDS
@@ -263,6 +266,11 @@ struct Geo {
     static constexpr bool LOOPSI = (kLoopSI || PTN > 11) && SI && NST % US == 0 && NST / US >= 2;
     static constexpr int R = LOOPSI ? RS : R0;
     static constexpr int LPS = KS * NFR;             // weight loads per stage per lane
+    // In place (INPL): the one decision of single-image mode that a two-image kernel can take on its
+    // own -- each conv reads image X and its epilogue, behind a workgroup barrier, writes X; staging and
+    // head scratch alias the group's image.  The looped conv, the chains, the select stores, the wave
+    // groups and the fused heads stay those of the two-image kernels (SI is false).
+    static constexpr bool INPL = WG == 5;
     // Global residual: when the fp32 residual stream (+ the accumulators) would need more than 256
     // VGPRs (F = 256 on 13x13: 2 x 176), it lives in a per-workgroup device scratch instead of
     // registers, lane-contiguous (one coalesced 1 KB store / load per wave and tile).
@@ -271,10 +279,12 @@ struct Geo {
     // accumulators + residual) the register allocator moves values between VGPRs and AGPRs, and a
     // copy of an inline-asm load's destination could be taken before the data lands; such kernels
     // (and the single-image ones) issue the ring with ordinary loads, which the compiler waits for.
-    static constexpr bool TRACKED = SI || LIVE_VGPRS > 300 || (P2 == 2 && (NB == 2 || WG == 2 || WG == 4));
+    static constexpr bool TRACKED = SI || LIVE_VGPRS > 300 || (P2 == 2 && (NB == 2 || WG == 2 || WG == 4 || WG == 5));
     static_assert(F % 64 == 0, "filters must be a multiple of 64");
     static_assert(!SI || NB == 1, "single-image mode takes one board per workgroup");
-    static_assert(WG == 1 || ((WG == 2 || WG == 4) && NB == 1 && !SI) || (WG == 3 && !SI && CT >= 1), "wave groups: two images");
+    static_assert(WG == 1 || ((WG == 2 || WG == 4 || WG == 5) && NB == 1 && !SI) || (WG == 3 && !SI && CT >= 1),
+                  "wave groups: two images, or one in place (INPL), never the single-image conv and heads");
+    static_assert(!INPL || (P == 3 && WRAP), "in place: the split F = 128 kernels");
     static_assert(!RG || SI, "the global residual is implemented for single-image kernels");
     static constexpr int RESID_BYTES = RG ? 4 * CT * TT * 64 * 16 : 0;   // per workgroup
     // P = 2: the lo image of each workgroup (device scratch after the grid's residual scratch)
@@ -1036,9 +1046,11 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
     // workgroup; LDS: image set 0 [WG][NB][ACT], image set 1 [WG][NB][ACT], bias table
     const int grp = NGR == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kThreads));
     char* X0 = smem + grp * NB * ACT;                                  // [NB][ACT]
-    char* X1 = SI ? smem : smem + NGR * NB * ACT + grp * NB * ACT;      // [NB][ACT]
+    // (in place: X1 is X0, the group's one image; group 0's scratch is the workgroup's first image)
+    constexpr bool INPL = G::INPL;
+    char* X1 = SI ? smem : INPL ? X0 : smem + NGR * NB * ACT + grp * NB * ACT;      // [NB][ACT]
     char* SCR = X1;                  // scratch aliases X1 while X1 holds no live activations
-    char* SCR0 = SI ? smem : smem + NGR * NB * ACT;   // group 0's scratch (the fused heads' shared features)
+    char* SCR0 = SI || INPL ? smem : smem + NGR * NB * ACT;   // group 0's scratch (the fused heads' shared features)
     float* btab = (float*)(smem + kp.btab_off);   // trunk conv biases [2B][F], after X1 / scratch
 
     const int board0 = (blockIdx.x * NGR + grp) * NB;
@@ -1132,7 +1144,8 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
     };
 
     for (int i = threadIdx.x; i < 2 * kp.B * F; i += kThreads * NGR) btab[i] = kp.bres[i];
-    for (int i = tid; i < NB * G::ZROWS * G::ROWS / 4; i += kThreads) {
+    // (in place: the staging scratch may cover these rows; they are zeroed after it, as X1's)
+    for (int i = tid; i < NB * G::ZROWS * G::ROWS / 4 && !INPL; i += kThreads) {
         const int bb = i / (G::ZROWS * G::ROWS / 4), j = i % (G::ZROWS * G::ROWS / 4);
         ((uint32_t*)(X0 + bb * ACT + NPOS * G::ROWS))[j] = 0u;
     }
@@ -1238,7 +1251,7 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
                 }
             }
         }
-        if constexpr (SI) __syncthreads();    // the image overwrites the im2col scratch
+        if constexpr (SI || INPL) __syncthreads();    // the image overwrites the im2col scratch
         // v2: the image feeding block 0 is the pre-activation act(BN_1(s)) of the stream
         const bool preact = V2 && kp.B > 0;
         f32x4* rg0 = rg;    // (residual tile addresses formed here, as in the tower's epilogues)
@@ -1454,6 +1467,7 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
         const float* b_a = btab + (2 * blk) * F;
         const float* b_b = b_a + F;
 
+        static_assert(!(INPL && kEpiInConv), "an epilogue inside the conv writes the other image");
         if constexpr (!V2 && G::LOOP && kEpiInConv) {
             // the same two epilogues as below, run per position tile inside each conv's last k-step
             float4 bia[CT];
@@ -1495,6 +1509,7 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
         }
         if constexpr (G::LOOP) conv3x3_looped<F, PTN, NB, P, WG>(X0, ring, acc, kp.wres, woff, (2 * blk) * G::NST, gmax, lane, bd);
         else conv3x3<F, PTN, NB, P, WG>(X0, ring, acc, kp.wres, woff, (2 * blk) * G::NST, gmax, lane, bd);
+        if constexpr (INPL) __syncthreads();    // in place: every wave's last read of the image, then its stores
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
             const int co = co_base + 16 * ct + 4 * g;
@@ -1513,6 +1528,7 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
 
         if constexpr (G::LOOP) conv3x3_looped<F, PTN, NB, P, WG>(X1, ring, acc, kp.wres, woff, (2 * blk + 1) * G::NST, gmax, lane, bd);
         else conv3x3<F, PTN, NB, P, WG>(X1, ring, acc, kp.wres, woff, (2 * blk + 1) * G::NST, gmax, lane, bd);
+        if constexpr (INPL) __syncthreads();
         if constexpr (V2) {   // s += SE(conv2 + bias); image = act(BN_1 of the next block (s)), model.py:128-149
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {
@@ -1746,6 +1762,16 @@ template <int F, int PTN, int P>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1)))
 trunk_kernel_h2(const KParams kp) {
     trunk_body<F, PTN, 1, 1, P, false, 4>(kp);
+}
+
+// Variant 23's decomposition with one image per board, overwritten in place, in 256 registers per
+// wave (variant 25): half the LDS and half the registers of trunk_kernel_h2, so two workgroups are
+// resident per CU (two waves per SIMD), each running at its own pace -- only workgroup barriers, no
+// synchronisation between the two.  Every row is computed as by the other split kernels.
+template <int F, int PTN, int P>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
+trunk_kernel_h2i(const KParams kp) {
+    trunk_body<F, PTN, 1, 2, P, false, 5>(kp);
 }
 
 template <int F, int PTN, int NB, int WPE, int P>

@@ -52,6 +52,7 @@ struct gz_net : PackSpec {         // d, fpad, p2, K0, cp, fp32, gemm_heads: wha
         bool fused_heads = false;  // the dense heads run inside the trunk kernel (no heads_kernel launch)
         int resid_bytes = 0;       // global residual scratch per workgroup
         int threads = 256;         // workgroup size (512: two wave groups)
+        int wgs_per_cu = 1;        // workgroups resident per CU (2: the in-place kernel, variant 25)
         std::string name;          // kernel name (rocprofv3's)
     } small, large;                // launches below / from large_min_rows rows
     int large_min_rows = 1 << 30;
@@ -113,7 +114,12 @@ extern "C" const char* gz_nn_last_error(void) { return g_err.c_str(); }
 // B-fragment reads per MFMA), 1-1.5 % faster than 21 at 1,024 rows (profiles/r05t_ab_v23.txt) and
 // bit-identical (the kernels build with -ffp-contract=on).  kLargeFallback: where kLargeVariant is
 // not compiled for a geometry.
+// Variant 25 (trunk_kernel_h2i: 23's decomposition with one image per board in place, 256 registers
+// per wave) is built for two workgroups per CU.  It takes the large launches only where two of its
+// workgroups fit the LDS side by side (2 x smem <= 160 KB: with the bias table in LDS, F = 128 nets of
+// up to 8 residual blocks) and the runtime reports two resident workgroups; otherwise 23 stays.
 constexpr int kSmallVariant = 11, kLargeVariant = 23, kLargeFallback = 21, kLargeMinRows = 257;
+constexpr int kLargeInPlace = 25;
 constexpr int kCUs = 256;
 
 static KernelChoice select_kernel(int fpad, int pt, int v, int precision, bool v2) {
@@ -186,6 +192,10 @@ extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
         if (kl.fn && !wg_fits(kl)) kl = KernelChoice{};
     }
     if (kc.fn && !wg_fits(kc)) kc = KernelChoice{};
+    // the two-workgroups-per-CU candidate for the large launches (decided below, with the device)
+    KernelChoice ki = !layerwise && getenv("GZ_KERNEL_VARIANT") == nullptr && kl.fn
+                          ? select_kernel(fpad, pt, kLargeInPlace, precision, v2) : KernelChoice{};
+    if (ki.fn && !wg_fits(ki)) ki = KernelChoice{};
     if (kc.fn && !kl.fn && vl != vs) {   // geometries with a single (one board per workgroup) variant
         kl = kc;
         min_large = 1 << 30;
@@ -225,12 +235,15 @@ extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
         t.fn = c.fn;
         t.nb = c.nb;
         t.threads = c.threads;
+        t.wgs_per_cu = c.wgs_per_cu;
         t.name = c.name;
         t.fused_heads = !c.single_image && !d.concat_all_layers;
         const int scr = t.fused_heads ? std::max(scr_in, fused_heads_bytes(npos, d.role_count, lgrow, gap_features(d), c.nb,
                                                                            c.groups == 2 ? 1 : c.nb, fpad))
                                       : scr_in;
+        // (in place: the scratch lies inside the images, wg_fits)
         t.btab_off = c.single_image ? align16(std::max(c.act_bytes, scr))
+                     : c.in_place   ? c.nb * c.act_bytes
                                     : c.nb * c.act_bytes + std::max(c.nb * c.act_bytes, scr);
         t.resid_bytes = c.resid_bytes;
         t.smem = t.btab_off + bias_table_bytes(fpad, d.residual_layers);
@@ -310,13 +323,27 @@ extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
         delete net;
         return nullptr;
     }
-    for (const gz_net::Trunk* t : {&net->small, &net->large}) {
+    // workgroups of a trunk kernel the runtime keeps resident per CU at its dynamic LDS size
+    auto resident = [&](const gz_net::Trunk& t) {
+        int nblk = 0;
+        if (t.smem > 64 * 1024 && hipFuncSetAttribute(t.fn, hipFuncAttributeMaxDynamicSharedMemorySize, t.smem) != hipSuccess)
+            return 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, t.fn, t.threads, t.smem) != hipSuccess) return 0;
+        return nblk;
+    };
+    if (ki.fn && net->large_min_rows < (1 << 30)) {
+        const gz_net::Trunk t = trunk(ki);
+        if (2 * t.smem <= 160 * 1024 && resident(t) >= t.wgs_per_cu) net->large = t;
+    }
+    for (gz_net::Trunk* t : {&net->small, &net->large}) {
         if (t->smem > 64 * 1024 &&
             hipFuncSetAttribute(t->fn, hipFuncAttributeMaxDynamicSharedMemorySize, t->smem) != hipSuccess) {
             fail("cannot raise dynamic LDS limit");
             delete net;
             return nullptr;
         }
+        // a fixed variant (GZ_KERNEL_VARIANT) reports what the device gives it
+        if (t->wgs_per_cu > 1) t->wgs_per_cu = std::max(1, std::min(t->wgs_per_cu, resident(*t)));
     }
     if (net->heads_smem > 64 * 1024 &&
         hipFuncSetAttribute(fp32 || net->f16 ? (const void*)&heads_kernel_blocked : (const void*)&heads_kernel,
@@ -780,5 +807,11 @@ extern "C" int gz_net_wave_rows(const gz_net* net) {
         const int gy = net->fpad / (32 * gzfp32::wave_co_tiles(net->fpad));
         return std::max(1, (kCUs / gy) * gzfp32::kTileCols / net->kp.npos);
     }
-    return (net->large_min_rows < (1 << 30) ? net->large.nb : net->small.nb) * kCUs;
+    const gz_net::Trunk& t = net->large_min_rows < (1 << 30) ? net->large : net->small;
+    return t.nb * t.wgs_per_cu * kCUs;
+}
+
+extern "C" int gz_net_workgroups_per_cu(const gz_net* net) {
+    if (!net || net->fp32 || net->layered) return 1;
+    return (net->large_min_rows < (1 << 30) ? net->large : net->small).wgs_per_cu;
 }

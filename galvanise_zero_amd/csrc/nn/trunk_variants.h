@@ -24,6 +24,8 @@ struct KernelChoice {
     int resid_bytes = 0;           // global residual scratch per workgroup (0: registers)
     int threads = 256;             // workgroup size (512: trunk_kernel8 / trunk_kernel_w8)
     int groups = 1;                // wave groups (2: trunk_kernel8, a board per group)
+    bool in_place = false;         // one image per board, overwritten in place, with the two-image kernels' heads
+    int wgs_per_cu = 1;            // workgroups per CU the kernel is built for (registers and LDS)
     char name[64] = {0};           // the kernel as rocprofv3 names it
 };
 
@@ -77,6 +79,20 @@ KernelChoice kernelh2_for() {
     return k;
 }
 
+// variant 23's groups with one image per board in place, two workgroups per CU (variant 25)
+template <int F, int PTN, int P>
+KernelChoice kernelh2i_for() {
+    KernelChoice k;
+    k.fn = (const void*)&trunk_kernel_h2i<F, PTN, P>;
+    k.act_bytes = Geo<F, PTN, 1, P, 5>::ACT_BYTES;
+    k.nb = 2;
+    k.groups = 2;
+    k.in_place = true;
+    k.wgs_per_cu = 2;
+    std::snprintf(k.name, sizeof(k.name), "gznn::trunk_kernel_h2i<%d, %d, %d>", F, PTN, P);
+    return k;
+}
+
 // precision 3: split (hi / lo) operands; otherwise bf16.  v = NB * 10 + WPE; 22 = two boards as two
 // groups of four waves (trunk_kernel8).
 template <int F, int PTN, bool V2 = false>
@@ -112,6 +128,7 @@ KernelChoice variants(int v, int precision) {
                         if constexpr (F == 128) {
                             if (v == 24) return kernelw8_for<F, PTN, 3>();
                             if (v == 23) return kernelh2_for<F, PTN, 3>();
+                            if (v == 25) return kernelh2i_for<F, PTN, 3>();
                         }
                     }
                 }

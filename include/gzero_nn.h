@@ -194,6 +194,11 @@ const char* gz_net_kernel_name(const gz_net* net, int large);
  * workgroup) is one workgroup per CU. */
 int gz_net_wave_rows(const gz_net* net);
 
+/* Workgroups of the large variant resident per CU: 2 for the in-place split kernel (trunk_kernel_h2i,
+ * where two of its workgroups fit the LDS and the runtime reports two), else 1.  gz_net_wave_rows
+ * counts them: boards per workgroup x workgroups per CU x 256 CUs. */
+int gz_net_workgroups_per_cu(const gz_net* net);
+
 /* Algorithmic FLOPs of one leaf evaluation (2 FLOP/MAC). */
 double gz_net_flops_per_eval(const gz_net* net);
 

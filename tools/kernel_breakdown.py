@@ -3,6 +3,9 @@ the cfg2 geometry at several residual-block counts: slope = time per residual bl
 intercept = everything else.  GPU box only.
 
 Usage: python tools/kernel_breakdown.py [--variants 12,13] [--batches 256,1024] [--precision fp32] [--pinned]
+Split precision (--precision fp32, the bf16x3 alias): variants 11, 21, 22, 23, 24 and 25 (trunk_kernel_h2i, two
+workgroups per CU: its GZ_STAMP phases are 23's, each workgroup stamping its own cycles while a
+neighbour shares the CU at launches of more than 512 rows).
 --pinned: planes and outputs in pinned host memory (the runner's zero-copy path), timed with events
 around a segmented launch, instead of gz_net_forward's device staging.
 """

@@ -1,5 +1,7 @@
 """Max |difference| of every output between two kernel variants (GZ_KERNEL_VARIANT) on cfg2-shaped
-nets of 0 / 1 / 6 residual blocks, at a few launch sizes.  Usage: python tools/variant_diff.py 21 23"""
+nets of 0 / 1 / 6 residual blocks, at a few launch sizes (split precision: variants 11, 21, 22, 23, 24
+and 25, the in-place two-workgroups-per-CU kernel).  Usage: python tools/variant_diff.py 21 23
+(or 23 25); 1,030 rows: more workgroups than CUs, so variant 25's run side by side."""
 import os
 import sys
 
@@ -14,7 +16,7 @@ va, vb = sys.argv[1], sys.argv[2]
 for blocks in (0, 1, 6):
     desc = NetDesc(12, 8, 8, 128, blocks, [155, 155])
     w = to_blob(random_weights(desc, 5, bias_std=0.2))
-    for n in (2, 33, 512):
+    for n in (2, 33, 512, 1030):
         x = random_planes(desc, n, 4)
         outs = []
         for v in (va, vb):
