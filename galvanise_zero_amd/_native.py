@@ -115,6 +115,26 @@ class GzSegment(ctypes.Structure):
                 ("values", ctypes.c_void_p)]
 
 
+class GzShadowStats(ctypes.Structure):
+    """gz_shadow_stats (include/gzero_nn.h): running totals of a net's shadow check."""
+    _fields_ = [("checks", ctypes.c_long), ("rows", ctypes.c_long), ("nonfinite_rows", ctypes.c_long),
+                ("policy_elems", ctypes.c_long), ("policy_rows", ctypes.c_long), ("value_elems", ctypes.c_long),
+                ("max_abs_dp", ctypes.c_double), ("sum_abs_dp", ctypes.c_double),
+                ("max_row_kl", ctypes.c_double), ("sum_row_kl", ctypes.c_double),
+                ("argmax_mismatch", ctypes.c_long),
+                ("max_abs_dv", ctypes.c_double), ("sum_abs_dv", ctypes.c_double),
+                ("worst_check", ctypes.c_long), ("worst_row", ctypes.c_long),
+                ("device_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        """The fields, plus the means they are the numerators of (0.0 where nothing was compared)."""
+        d = {n: getattr(self, n) for n, _ in self._fields_}
+        d["mean_abs_dp"] = d["sum_abs_dp"] / d["policy_elems"] if d["policy_elems"] else 0.0
+        d["mean_row_kl"] = d["sum_row_kl"] / d["policy_rows"] if d["policy_rows"] else 0.0
+        d["mean_abs_dv"] = d["sum_abs_dv"] / d["value_elems"] if d["value_elems"] else 0.0
+        return d
+
+
 def nn_lib():
     lib = _load("libgz_nn.so")
     if not getattr(lib, "_gz_typed", False):
@@ -154,6 +174,18 @@ def nn_lib():
             lib.gz_net_workgroups_per_cu.restype = ctypes.c_int
             lib.gz_net_workgroups_per_cu.argtypes = [ctypes.c_void_p]
         lib.gz_nn_last_error.restype = ctypes.c_char_p
+        if hasattr(lib, "gz_shadow_stats_sizeof"):   # (absent from older A/B builds loaded through GZ_LIB_DIR)
+            lib.gz_shadow_stats_sizeof.restype = ctypes.c_size_t
+            lib.gz_shadow_stats_sizeof.argtypes = []
+            if lib.gz_shadow_stats_sizeof() != ctypes.sizeof(GzShadowStats):
+                raise RuntimeError("gz_shadow_stats is %d bytes in libgz_nn.so, %d in GzShadowStats"
+                                   % (lib.gz_shadow_stats_sizeof(), ctypes.sizeof(GzShadowStats)))
+            lib.gz_net_shadow_enable.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+            lib.gz_net_shadow_disable.argtypes = [ctypes.c_void_p]
+            lib.gz_net_shadow_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(GzShadowStats), ctypes.c_int]
+            lib.gz_nn_compare_outputs.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                                  ctypes.c_int, ctypes.POINTER(_FP), _FP, ctypes.POINTER(_FP), _FP,
+                                                  ctypes.POINTER(GzShadowStats)]
         lib._gz_typed = True
     return lib
 
@@ -188,6 +220,28 @@ def make_net_desc(desc, precision=GZ_PRECISION_BF16):
 
 def _fptr(a):
     return a.ctypes.data_as(_FP)
+
+
+def compare_outputs(outs_a, outs_b, device=0):
+    """The shadow check's comparison alone (gz_nn_compare_outputs), on the GPU: outs_a ("got", the
+    net's) and outs_b ("ref", the shadow's) are lists [policy_0 .. policy_{R-1}, values] as
+    HipNet.forward returns them.  Returns the gz_shadow_stats of that one check as a dict (with
+    mean_abs_dp, mean_row_kl, mean_abs_dv)."""
+    lib = nn_lib()
+    a = [np.ascontiguousarray(x, dtype=np.float32) for x in outs_a]
+    b = [np.ascontiguousarray(x, dtype=np.float32) for x in outs_b]
+    if len(a) != len(b) or len(a) < 2 or any(x.ndim != 2 or x.shape != y.shape for x, y in zip(a, b)) or \
+            any(x.shape[0] != a[0].shape[0] for x in a):
+        raise ValueError("compare_outputs: two lists of [n, P_r] policies and [n, V] values of equal shapes")
+    roles = len(a) - 1
+    sizes = (ctypes.c_int * roles)(*[x.shape[1] for x in a[:-1]])
+    pa = (_FP * roles)(*[_fptr(x) for x in a[:-1]])
+    pb = (_FP * roles)(*[_fptr(x) for x in b[:-1]])
+    st = GzShadowStats()
+    if lib.gz_nn_compare_outputs(device, a[0].shape[0], roles, sizes, a[-1].shape[1], pa, _fptr(a[-1]), pb, _fptr(b[-1]),
+                                 ctypes.byref(st)) != 0:
+        raise RuntimeError("gz_nn_compare_outputs failed: %s" % lib.gz_nn_last_error().decode())
+    return st.as_dict()
 
 
 class HipNet(object):
@@ -285,6 +339,29 @@ class HipNet(object):
     def set_output_logits(self, on=True):
         """Diagnostics: later forwards return the heads' pre-activation outputs (logits)."""
         self._check(self.lib.gz_net_set_output_logits(self.handle, int(bool(on))), "gz_net_set_output_logits")
+
+    def enable_shadow(self, precision, every=64, max_rows=256):
+        """Give the net a shadow: the same description and weights in arithmetic mode `precision`
+        (a name of PRECISIONS).  From the next set_weights / set_weights_device on, every `every`-th
+        forward also runs its first `max_rows` rows through the shadow and compares the two sets of
+        outputs on the GPU (gz_net_shadow_enable, include/gzero_nn.h); shadow_stats() reads the totals."""
+        self._check(self.lib.gz_net_shadow_enable(self.handle, PRECISIONS[canonical_precision(precision)], every, max_rows),
+                    "gz_net_shadow_enable")
+
+    def disable_shadow(self):
+        self._check(self.lib.gz_net_shadow_disable(self.handle), "gz_net_shadow_disable")
+
+    def shadow_stats_raw(self, reset=False):
+        """The GzShadowStats of shadow_stats()."""
+        st = GzShadowStats()
+        self._check(self.lib.gz_net_shadow_stats(self.handle, ctypes.byref(st), int(bool(reset))), "gz_net_shadow_stats")
+        return st
+
+    def shadow_stats(self, reset=False):
+        """Totals of the shadow checks completed so far (gz_shadow_stats as a dict, plus mean_abs_dp,
+        mean_row_kl and mean_abs_dv); waits for nothing, safe while a runner launches on the net.
+        reset=True: later totals start from zero."""
+        return self.shadow_stats_raw(reset).as_dict()
 
     def stamp_avg(self):
         out = (ctypes.c_double * 8)()

@@ -8,6 +8,7 @@
 #include "trunk_variants.h"
 #include "fp32_forward.h"
 #include "layered_forward.h"
+#include "shadow_compare.h"
 #include "weight_image.h"
 #include "../../../include/gzero_nn.h"
 
@@ -17,6 +18,7 @@
 #include <map>
 #include <mutex>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -90,6 +92,37 @@ struct gz_net : PackSpec {         // d, fpad, p2, K0, cp, fp32, gemm_heads: wha
     int layered = 0;
     std::map<hipStream_t, int*> bexp;
     int in_width() const { return layered ? K0 : cp; }   // input channels of the initial conv's launch
+    // the shadow check (gzero_nn.h gz_net_shadow_enable): `shadow` is read by launches under wmu and by
+    // gz_net_shadow_stats under shadow_mu, and changed under both (lock order wmu, shadow_mu)
+    struct Shadow;
+    Shadow* shadow = nullptr;
+    std::mutex shadow_mu;
+    bool is_shadow = false;        // a shadow has none of its own and is reached through its net alone
+};
+
+// A net's shadow: the second net, the device block of running totals, and a ring of pinned snapshots
+// of that block, one per check in flight, each with the events around its check.
+struct gz_net::Shadow {
+    static constexpr int kSlots = 8;
+    gz_net* net = nullptr;         // same desc, another precision; its images are installed under the owner's wmu
+    int every = 64, max_rows = 256;
+    bool from_env = false;         // GZ_NN_SHADOW: gz_net_destroy prints the totals
+    long forwards = 0;             // the owner's forwards of n > 0 since the enable
+    gz_shadow_stats* d_acc = nullptr;        // the cumulative block (device)
+    struct Out { float* out = nullptr; gzshadow::RowRecord* rec = nullptr; };
+    std::map<hipStream_t, Out> out;          // the shadow's outputs [max_rows][sum P_r + V] and row records, per stream
+    struct Slot {
+        gz_shadow_stats* host = nullptr;     // pinned
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        bool pending = false;
+        long epoch = 0;
+    } slot[kSlots];
+    int next = 0;                  // the slot of the next check (the ring is harvested oldest first from here)
+    hipStream_t last_stream = nullptr;
+    int last_slot = -1;
+    long epoch = 0;                // bumped by a reset: snapshots of earlier epochs are dropped
+    bool fresh = true;             // the next check's fold starts the block from zero
+    gz_shadow_stats done{};        // the newest completed snapshot of this epoch, device_ms summed
 };
 
 extern "C" const char* gz_nn_last_error(void) { return g_err.c_str(); }
@@ -127,9 +160,8 @@ static KernelChoice select_kernel(int fpad, int pt, int v, int precision, bool v
     return trunk_variant(fpad, pt, v, precision, v2);
 }
 
-extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
-    if (!desc) { fail("null desc"); return nullptr; }
-    const gz_net_desc& d = *desc;
+// gz_net_create's first half: every refusal that needs no device, and the net's host-side state.
+static gz_net* create_host(const gz_net_desc& d, int device, gz_net::Trunk* in_place) {
     if (d.cnn_kernel_size != 3) { fail("only cnn_kernel_size 3 is supported"); return nullptr; }
     if (d.role_count < 1 || d.role_count > GZ_MAX_ROLES) { fail("role_count out of range"); return nullptr; }
     if (d.num_values < 1 || d.num_values > 4) { fail("num_values out of range"); return nullptr; }
@@ -317,6 +349,15 @@ extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
             return nullptr;
         }
     }
+    // the two-workgroups-per-CU candidate for the large launches (create_device decides, with the device)
+    *in_place = ki.fn && net->large_min_rows < (1 << 30) ? trunk(ki) : gz_net::Trunk{};
+    return net;
+}
+
+// gz_net_create's second half: the net's stream and events, the kernels' LDS limits and residency.
+// Deletes the net on failure.
+static gz_net* create_device(gz_net* net, const gz_net::Trunk& in_place) {
+    const int device = net->device;
     if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&net->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreate(&net->ev0) != hipSuccess || hipEventCreate(&net->ev1) != hipSuccess) {
         fail(std::string("HIP init failed: ") + hipGetErrorString(hipGetLastError()));
@@ -331,8 +372,8 @@ extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, t.fn, t.threads, t.smem) != hipSuccess) return 0;
         return nblk;
     };
-    if (ki.fn && net->large_min_rows < (1 << 30)) {
-        const gz_net::Trunk t = trunk(ki);
+    if (in_place.fn) {
+        const gz_net::Trunk& t = in_place;
         if (2 * t.smem <= 160 * 1024 && resident(t) >= t.wgs_per_cu) net->large = t;
     }
     for (gz_net::Trunk* t : {&net->small, &net->large}) {
@@ -346,7 +387,7 @@ extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
         if (t->wgs_per_cu > 1) t->wgs_per_cu = std::max(1, std::min(t->wgs_per_cu, resident(*t)));
     }
     if (net->heads_smem > 64 * 1024 &&
-        hipFuncSetAttribute(fp32 || net->f16 ? (const void*)&heads_kernel_blocked : (const void*)&heads_kernel,
+        hipFuncSetAttribute(net->fp32 || net->f16 ? (const void*)&heads_kernel_blocked : (const void*)&heads_kernel,
                             hipFuncAttributeMaxDynamicSharedMemorySize, net->heads_smem) != hipSuccess) {
         fail("cannot raise dynamic LDS limit (heads)");
         delete net;
@@ -355,9 +396,215 @@ extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
     return net;
 }
 
+// ---- the shadow check (gzero_nn.h) -----------------------------------------------------------------
+namespace {
+int net_precision(const gz_net_desc& d) { return d.precision == 0 ? GZ_PRECISION_BF16 : d.precision; }
+
+// The refusals of gz_net_shadow_enable that need no device, then the shadow's host half: NULL with
+// "shadow: ..." in g_err, or the shadow net (create_device still to run).
+gz_net* shadow_host(const gz_net_desc& d, int device, int precision, int every, int max_rows, gz_net::Trunk* in_place) {
+    if (precision == 0) precision = GZ_PRECISION_BF16;
+    if (precision == net_precision(d)) {
+        fail("shadow: precision " + std::to_string(precision) + " is the net's own mode");
+        return nullptr;
+    }
+    if (every < 1 || max_rows < 1) {
+        fail("shadow: every and max_rows must be at least 1");
+        return nullptr;
+    }
+    gz_net_desc sd = d;
+    sd.precision = precision;
+    gz_net* s = create_host(sd, device, in_place);
+    if (!s) {
+        fail("shadow: " + g_err);
+        return nullptr;
+    }
+    s->is_shadow = true;
+    return s;
+}
+
+// GZ_NN_SHADOW=<precision>[:<every>[:<max_rows>]]: 1 parsed, 0 unset, -1 malformed (g_err)
+int shadow_env(int* precision, int* every, int* max_rows) {
+    const char* e = getenv("GZ_NN_SHADOW");
+    if (!e || !*e) return 0;
+    long v[3] = {0, 64, 256};
+    int got = 0;
+    const char* p = e;
+    bool ok = true;
+    while (ok && got < 3) {
+        char* end = nullptr;
+        const long x = strtol(p, &end, 10);
+        ok = end != p && x >= 0 && x <= (1 << 20);
+        v[got++] = x;
+        p = end;
+        if (!ok || *p == 0) break;
+        ok = *p == ':' && got < 3;
+        ++p;
+    }
+    if (!ok || *p != 0 || v[1] < 1 || v[2] < 1) {
+        fail(std::string("GZ_NN_SHADOW: expected <precision>[:<every>[:<max_rows>]] with every and max_rows >= 1, got \"") + e + "\"");
+        return -1;
+    }
+    *precision = (int)v[0];
+    *every = (int)v[1];
+    *max_rows = (int)v[2];
+    return 1;
+}
+
+void shadow_free(gz_net::Shadow* sh) {   // (after a device sync, or before any launch)
+    if (!sh) return;
+    if (sh->net) gz_net_destroy(sh->net);
+    if (sh->d_acc) (void)hipFree(sh->d_acc);
+    for (auto& o : sh->out) (void)hipFree(o.second.out);   // (one allocation: the records follow the outputs)
+    for (auto& s : sh->slot) {
+        if (s.host) (void)hipHostFree(s.host);
+        if (s.e0) (void)hipEventDestroy(s.e0);
+        if (s.e1) (void)hipEventDestroy(s.e1);
+    }
+    delete sh;
+}
+
+// The device half of an enable: the shadow net's, the totals block and the snapshot ring.  Takes
+// over (and on failure frees) the shadow net s.
+int shadow_attach(gz_net* net, gz_net* s, const gz_net::Trunk& in_place, int every, int max_rows, bool from_env) {
+    if (!create_device(s, in_place)) return fail("shadow: " + g_err);
+    gz_net::Shadow* sh = new gz_net::Shadow;
+    sh->net = s;
+    sh->every = every;
+    sh->max_rows = max_rows;
+    sh->from_env = from_env;
+    s->kp.logits = net->kp.logits;
+    hipError_t e = hipMalloc((void**)&sh->d_acc, sizeof(gz_shadow_stats));
+    for (auto& sl : sh->slot) {
+        if (e == hipSuccess) e = hipHostMalloc((void**)&sl.host, sizeof(gz_shadow_stats), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipEventCreate(&sl.e0);
+        if (e == hipSuccess) e = hipEventCreate(&sl.e1);
+    }
+    if (e != hipSuccess) {
+        shadow_free(sh);
+        return fail(std::string("shadow: ") + hipGetErrorString(e));
+    }
+    std::lock_guard<std::mutex> wl(net->wmu);
+    std::lock_guard<std::mutex> sl(net->shadow_mu);
+    net->shadow = sh;
+    return 0;
+}
+
+// Takes what has completed off the ring, oldest first (shadow_mu held): device_ms grows by each
+// completed check's, `done` becomes the newest completed snapshot.  wait_slot >= 0: first wait for
+// that slot's check (the ring is full, or the shadow is going away).
+void shadow_harvest(gz_net::Shadow* sh, int wait_slot = -1) {
+    if (wait_slot >= 0 && sh->slot[wait_slot].pending) (void)hipEventSynchronize(sh->slot[wait_slot].e1);
+    for (int k = 0; k < gz_net::Shadow::kSlots; ++k) {
+        gz_net::Shadow::Slot& s = sh->slot[(sh->next + k) % gz_net::Shadow::kSlots];
+        if (!s.pending) continue;
+        if (hipEventQuery(s.e1) != hipSuccess) break;   // (in issue order: a later one is not taken before it)
+        s.pending = false;
+        if (s.epoch != sh->epoch) continue;             // issued before the last reset
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, s.e0, s.e1);
+        const double total = sh->done.device_ms + (double)ms;
+        sh->done = *s.host;
+        sh->done.device_ms = total;
+    }
+}
+}  // namespace
+
+extern "C" gz_net* gz_net_create(const gz_net_desc* desc, int device) {
+    if (!desc) { fail("null desc"); return nullptr; }
+    gz_net::Trunk in_place, s_in_place;
+    gz_net* net = create_host(*desc, device, &in_place);
+    if (!net) return nullptr;
+    // GZ_NN_SHADOW (diagnostics): the spec and the shadow's geometry, still in front of the device
+    gz_net* s = nullptr;
+    int sp = 0, every = 0, max_rows = 0;
+    const int env = shadow_env(&sp, &every, &max_rows);
+    if (env > 0) s = shadow_host(*desc, device, sp, every, max_rows, &s_in_place);
+    if (env < 0 || (env > 0 && !s)) {
+        delete net;
+        return nullptr;
+    }
+    net = create_device(net, in_place);
+    if (!net) {
+        delete s;
+        return nullptr;
+    }
+    if (s && shadow_attach(net, s, s_in_place, every, max_rows, true)) {
+        const std::string msg = g_err;
+        gz_net_destroy(net);
+        g_err = msg;
+        return nullptr;
+    }
+    return net;
+}
+
+extern "C" size_t gz_shadow_stats_sizeof(void) { return sizeof(gz_shadow_stats); }
+
+extern "C" int gz_net_shadow_enable(gz_net* net, int precision, int every, int max_rows) {
+    if (!net) return fail("null net");
+    if (net->is_shadow) return fail("shadow: a shadow cannot have a shadow of its own");
+    {
+        std::lock_guard<std::mutex> sl(net->shadow_mu);
+        if (net->shadow) return fail("shadow: the net already has a shadow");
+    }
+    gz_net::Trunk in_place;
+    gz_net* s = shadow_host(net->d, net->device, precision, every, max_rows, &in_place);
+    if (!s) return -1;
+    return shadow_attach(net, s, in_place, every, max_rows, false);
+}
+
+extern "C" int gz_net_shadow_disable(gz_net* net) {
+    if (!net) return fail("null net");
+    gz_net::Shadow* sh = nullptr;
+    {
+        std::lock_guard<std::mutex> wl(net->wmu);
+        std::lock_guard<std::mutex> sl(net->shadow_mu);
+        sh = net->shadow;
+        net->shadow = nullptr;
+    }
+    if (!sh) return fail("shadow: the net has no shadow");
+    HIPCHK(hipSetDevice(net->device));
+    HIPCHK(hipDeviceSynchronize());   // checks still queued read the shadow's buffers
+    shadow_free(sh);
+    return 0;
+}
+
+extern "C" int gz_net_shadow_stats(gz_net* net, gz_shadow_stats* out, int reset) {
+    if (!net || !out) return fail("null argument");
+    std::lock_guard<std::mutex> sl(net->shadow_mu);
+    gz_net::Shadow* sh = net->shadow;
+    if (!sh) return fail("shadow: the net has no shadow");
+    shadow_harvest(sh);
+    *out = sh->done;
+    if (reset) {
+        ++sh->epoch;
+        sh->fresh = true;
+        sh->done = gz_shadow_stats{};
+    }
+    return 0;
+}
+
 extern "C" void gz_net_destroy(gz_net* net) {
     if (!net) return;
     (void)hipSetDevice(net->device);
+    if (gz_net::Shadow* sh = net->shadow) {
+        (void)hipDeviceSynchronize();
+        if (sh->from_env) {
+            shadow_harvest(sh);
+            const gz_shadow_stats& t = sh->done;
+            const long ok = t.rows - t.nonfinite_rows;
+            fprintf(stderr,
+                    "gz_nn shadow (precision %d vs %d, every %d, max_rows %d): checks %ld rows %ld nonfinite_rows %ld "
+                    "max_abs_dp %.6g mean_abs_dp %.6g max_row_kl %.6g mean_row_kl %.6g argmax_mismatch %ld of %ld "
+                    "max_abs_dv %.6g mean_abs_dv %.6g worst check %ld row %ld device_ms %.3f\n",
+                    net_precision(net->d), net_precision(sh->net->d), sh->every, sh->max_rows, t.checks, t.rows, t.nonfinite_rows,
+                    t.max_abs_dp, t.policy_elems ? t.sum_abs_dp / t.policy_elems : 0.0, t.max_row_kl,
+                    t.policy_rows ? t.sum_row_kl / t.policy_rows : 0.0, t.argmax_mismatch, ok * net->d.role_count, t.max_abs_dv,
+                    t.value_elems ? t.sum_abs_dv / t.value_elems : 0.0, t.worst_check, t.worst_row, t.device_ms);
+        }
+        net->shadow = nullptr;
+        shadow_free(sh);
+    }
     if (net->dmem) (void)hipFree(net->dmem);
     if (net->d_io) (void)hipFree(net->d_io);
     if (net->d_stamps) (void)hipFree(net->d_stamps);
@@ -393,9 +640,11 @@ namespace {
 // Swaps in the device image m (laid out by I) under the lock launch_segments takes, so a launcher
 // thread running a generation roll sees either the old or the new image, never a mix; the replaced
 // image is freed after a device sync (launches already queued may still read it).
-int install_image(gz_net* net, char* m, const ImageLayout& I) {
+// (swap_image: one net's pointers, its owner's wmu held; returns the replaced image.)  A net with a
+// shadow installs both nets' images in that one critical section: a launch compares two nets of one
+// generation.
+char* swap_image(gz_net* net, char* m, const ImageLayout& I) {
     const int R = net->d.role_count;
-    std::unique_lock<std::mutex> wl(net->wmu);
     char* old = net->dmem;
     net->dmem = m;
     KParams& kp = net->kp;
@@ -424,12 +673,32 @@ int install_image(gz_net* net, char* m, const ImageLayout& I) {
     for (int r = 0; r < R; ++r) kp.pdp[r] = net->gemm_heads ? (const __bf16*)(m + I.pdp[r]) : nullptr;
     net->has_weights = true;
     net->image_bytes = I.total;
+    return old;
+}
+
+int install_image(gz_net* net, char* m, const ImageLayout& I, char* sm = nullptr, const ImageLayout* sI = nullptr) {
+    std::unique_lock<std::mutex> wl(net->wmu);
+    char* old = swap_image(net, m, I);
+    char* sold = nullptr;
+    if (sm && net->shadow) {
+        sold = swap_image(net->shadow->net, sm, *sI);
+    } else if (sm) {   // the shadow went away (gz_net_shadow_disable) while its image was built
+        sold = sm;
+    }
     wl.unlock();
-    if (old) {
+    if (old || sold) {
         HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipFree(old));
+        if (old) HIPCHK(hipFree(old));
+        if (sold) HIPCHK(hipFree(sold));
     }
     return 0;
+}
+
+// the shadow net of `net` at this moment (NULL: none)
+gz_net* shadow_of(gz_net* net) {
+    if (!net || net->is_shadow) return nullptr;
+    std::lock_guard<std::mutex> sl(net->shadow_mu);
+    return net->shadow ? net->shadow->net : nullptr;
 }
 
 int check_count(const gz_net* net, const float* blob, size_t count) {
@@ -453,7 +722,8 @@ __global__ void pack_kernel(const Job* jobs, const float* blob, const float* fol
 }
 }  // namespace
 
-extern "C" int gz_net_set_weights(gz_net* net, const float* blob, size_t count) {
+// One net's device image of a host blob: *m (to be installed, or freed by the caller) laid out by *I.
+static int build_image_host(gz_net* net, const float* blob, size_t count, char** mp, ImageLayout* Ip) {
     if (check_count(net, blob, count)) return -1;
     const ImageLayout I = image_layout(*net);
     std::vector<char> img(I.total, 0);
@@ -473,7 +743,22 @@ extern "C" int gz_net_set_weights(gz_net* net, const float* blob, size_t count) 
         (void)hipFree(m);
         return fail("weight upload failed");
     }
-    return install_image(net, m, I);
+    *mp = m;
+    *Ip = I;
+    return 0;
+}
+
+extern "C" int gz_net_set_weights(gz_net* net, const float* blob, size_t count) {
+    char *m = nullptr, *sm = nullptr;
+    ImageLayout I, sI;
+    if (build_image_host(net, blob, count, &m, &I)) return -1;
+    if (gz_net* s = shadow_of(net)) {   // both nets take the blob, or neither
+        if (build_image_host(s, blob, count, &sm, &sI)) {
+            (void)hipFree(m);
+            return fail("shadow: " + g_err);
+        }
+    }
+    return install_image(net, m, I, sm, &sI);
 }
 
 // The same jobs on the device (generation roll: the blob arrives in HBM by an RCCL broadcast), the
@@ -481,14 +766,7 @@ extern "C" int gz_net_set_weights(gz_net* net, const float* blob, size_t count) 
 // fp16x3-layered: the blob's BN-folded conv weights must lie within fp16's finite range (a
 // precondition here, checked by gz_net_set_weights only): a larger one becomes an infinite hi part
 // and non-finite outputs; nothing is clamped.
-extern "C" int gz_net_set_weights_device(gz_net* net, const float* d_blob, size_t count) {
-    if (check_count(net, d_blob, count)) return -1;
-    if (getenv("GZ_HOST_WEIGHT_ROLL")) {   // diagnostics: the round-trip path (D2H, host fold / pack, H2D)
-        std::vector<float> h(count);
-        HIPCHK(hipSetDevice(net->device));
-        HIPCHK(hipMemcpy(h.data(), d_blob, count * 4, hipMemcpyDeviceToHost));
-        return gz_net_set_weights(net, h.data(), count);
-    }
+static int build_image_device(gz_net* net, const float* d_blob, size_t count, char** mp, ImageLayout* Ip) {
     const ImageLayout I = image_layout(*net);
     const JobList J = job_list(*net, blob_plan(net->d), I);
     HIPCHK(hipSetDevice(net->device));
@@ -537,7 +815,29 @@ extern "C" int gz_net_set_weights_device(gz_net* net, const float* d_blob, size_
     (void)hipEventElapsedTime(&ms, e0, e1);
     net->last_roll_ms = ms;
     cleanup();
-    return install_image(net, m, I);
+    *mp = m;
+    *Ip = I;
+    return 0;
+}
+
+extern "C" int gz_net_set_weights_device(gz_net* net, const float* d_blob, size_t count) {
+    if (check_count(net, d_blob, count)) return -1;
+    if (getenv("GZ_HOST_WEIGHT_ROLL")) {   // diagnostics: the round-trip path (D2H, host fold / pack, H2D)
+        std::vector<float> h(count);
+        HIPCHK(hipSetDevice(net->device));
+        HIPCHK(hipMemcpy(h.data(), d_blob, count * 4, hipMemcpyDeviceToHost));
+        return gz_net_set_weights(net, h.data(), count);
+    }
+    char *m = nullptr, *sm = nullptr;
+    ImageLayout I, sI;
+    if (build_image_device(net, d_blob, count, &m, &I)) return -1;
+    if (gz_net* s = shadow_of(net)) {   // both nets take the blob, or neither
+        if (build_image_device(s, d_blob, count, &sm, &sI)) {
+            (void)hipFree(m);
+            return fail("shadow: " + g_err);
+        }
+    }
+    return install_image(net, m, I, sm, &sI);
 }
 
 
@@ -555,12 +855,11 @@ extern "C" size_t gz_net_copy_weight_image(gz_net* net, void* out, size_t cap) {
     return n;
 }
 
-static int launch_segments(gz_net* net, hipStream_t stream, const gz_segment* segs, int nseg,
-                           hipEvent_t mid = nullptr) {
+// One net's forward, queued on `stream`; *rows = the launch's rows.  The caller holds the wmu that
+// guards the net's weight pointers (its own, or its owner's for a shadow).
+static int launch_net(gz_net* net, hipStream_t stream, const gz_segment* segs, int nseg, hipEvent_t mid, int* rows) {
+    *rows = 0;
     if (nseg < 1 || nseg > kMaxSegments) return fail("segment count out of range (1.." + std::to_string(kMaxSegments) + ")");
-    // the weight image stays valid until this launch is queued (gz_net_set_weights frees a replaced
-    // image only after a device sync)
-    std::lock_guard<std::mutex> wl(net->wmu);
     if (!net->has_weights) return fail("weights not set");
     KParams kp = net->kp;
     int n = 0;
@@ -574,6 +873,7 @@ static int launch_segments(gz_net* net, hipStream_t stream, const gz_segment* se
         n += segs[i].rows;
     }
     if (n <= 0) return 0;
+    *rows = n;
     kp.n = n;
     kp.nseg = nseg;
     kp.stamps = net->stamps_on ? net->d_stamps : nullptr;
@@ -695,14 +995,101 @@ static int launch_segments(gz_net* net, hipStream_t stream, const gz_segment* se
     return 0;
 }
 
+// The shadow check of a launch of n rows just queued on `stream` (net->wmu held): the first
+// min(n, max_rows) rows through the shadow net into its own buffer, the comparison against the
+// outputs `segs` point to, and an asynchronous snapshot of the totals into the ring.
+static int shadow_check(gz_net* net, hipStream_t stream, const gz_segment* segs, int nseg, int n) {
+    std::lock_guard<std::mutex> sl(net->shadow_mu);
+    gz_net::Shadow* sh = net->shadow;
+    const long index = sh->forwards++;
+    gz_net* s = sh->net;
+    if (index % sh->every != 0 || !s->has_weights) return 0;
+    const gz_net_desc& d = net->d;
+    const int R = d.role_count, V = d.num_values, k = std::min(n, sh->max_rows);
+    size_t out_f = V;
+    for (int r = 0; r < R; ++r) out_f += d.policy_dist_count[r];
+    gz_net::Shadow::Out& o = sh->out[stream];
+    if (!o.out) {   // this stream's outputs [max_rows][sum P_r + V], then its row records
+        const size_t out_bytes = ((size_t)sh->max_rows * out_f * sizeof(float) + 15) & ~(size_t)15;
+        HIPCHK(hipMalloc((void**)&o.out, out_bytes + (size_t)sh->max_rows * sizeof(gzshadow::RowRecord)));
+        o.rec = (gzshadow::RowRecord*)((char*)o.out + out_bytes);
+    }
+    shadow_harvest(sh);
+    gz_net::Shadow::Slot& slot = sh->slot[sh->next];
+    if (slot.pending) shadow_harvest(sh, sh->next);   // the ring is full: wait for its oldest check
+    // the totals block has one writer at a time: a check on another stream follows the last one
+    if (sh->last_slot >= 0 && sh->last_stream != stream && sh->slot[sh->last_slot].pending)
+        HIPCHK(hipStreamWaitEvent(stream, sh->slot[sh->last_slot].e1, 0));
+    HIPCHK(hipEventRecord(slot.e0, stream));
+    // the truncated segment list: the net's planes, the shadow's buffer; the same rows of the net's outputs
+    gz_segment ss[GZ_MAX_SEGMENTS];
+    gzshadow::CompareArgs ca{};
+    float* pol_b[GZ_MAX_ROLES];
+    float* p = o.out;
+    for (int r = 0; r < R; ++r) {
+        pol_b[r] = p;
+        p += (size_t)sh->max_rows * d.policy_dist_count[r];
+        ca.pol_b[r] = pol_b[r];
+        ca.P[r] = d.policy_dist_count[r];
+    }
+    ca.val_b = p;
+    int m = 0, row0 = 0;
+    for (int i = 0; i < nseg && row0 < k; ++i) {
+        if (segs[i].rows <= 0) continue;
+        gz_segment& g = ss[m];
+        g = segs[i];
+        g.rows = std::min(segs[i].rows, k - row0);
+        ca.seg[m].row0 = row0;
+        for (int r = 0; r < R; ++r) {
+            ca.seg[m].pol[r] = segs[i].policies[r];
+            g.policies[r] = pol_b[r] + (size_t)row0 * d.policy_dist_count[r];
+        }
+        ca.seg[m].val = segs[i].values;
+        g.values = p + (size_t)row0 * V;
+        row0 += g.rows;
+        ++m;
+    }
+    int srows = 0;
+    if (launch_net(s, stream, ss, m, nullptr, &srows)) return fail("shadow: " + g_err);
+    ca.nseg = m;
+    ca.n = k;
+    ca.R = R;
+    ca.V = V;
+    ca.logits = net->kp.logits;
+    ca.rec = o.rec;
+    if (const char* e = gzshadow::launch_compare(ca, index, sh->fresh ? 1 : 0, sh->d_acc, stream)) return fail(std::string("shadow: ") + e);
+    sh->fresh = false;
+    HIPCHK(hipMemcpyAsync(slot.host, sh->d_acc, sizeof(gz_shadow_stats), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipEventRecord(slot.e1, stream));
+    slot.pending = true;
+    slot.epoch = sh->epoch;
+    sh->last_slot = sh->next;
+    sh->last_stream = stream;
+    sh->next = (sh->next + 1) % gz_net::Shadow::kSlots;
+    return 0;
+}
+
+// `end` (may be NULL) is recorded after the net's own launches, before a shadow check's.
+static int launch_segments(gz_net* net, hipStream_t stream, const gz_segment* segs, int nseg,
+                           hipEvent_t mid = nullptr, hipEvent_t end = nullptr) {
+    // the weight image stays valid until this launch is queued (gz_net_set_weights frees a replaced
+    // image only after a device sync)
+    std::lock_guard<std::mutex> wl(net->wmu);
+    int n = 0;
+    if (launch_net(net, stream, segs, nseg, mid, &n)) return -1;
+    if (end) HIPCHK(hipEventRecord(end, stream));
+    if (n > 0 && net->shadow) return shadow_check(net, stream, segs, nseg, n);
+    return 0;
+}
+
 static int launch(gz_net* net, hipStream_t stream, const float* d_planes, int n,
-                  float* const* d_pol, float* d_val) {
+                  float* const* d_pol, float* d_val, hipEvent_t end = nullptr) {
     gz_segment sg{};
     sg.rows = n;
     sg.planes = d_planes;
     for (int r = 0; r < net->kp.R; ++r) sg.policies[r] = d_pol[r];
     sg.values = d_val;
-    return launch_segments(net, stream, &sg, 1);
+    return launch_segments(net, stream, &sg, 1, nullptr, end);
 }
 
 extern "C" int gz_net_forward_device(gz_net* net, void* stream, const float* d_planes, int n,
@@ -752,10 +1139,10 @@ extern "C" int gz_net_forward(gz_net* net, const float* planes, int n, float* co
     if (stamps) HIPCHK(hipMemsetAsync(net->d_stamps, 0, (size_t)grid * 8 * sizeof(unsigned long long), net->stream));
     HIPCHK(hipEventRecord(net->ev0, net->stream));
     net->stamps_on = stamps;
-    const int lrc = launch(net, net->stream, d_in, n, d_pol, d_val);
+    // (ev1 follows the net's own launches: a shadow check's work comes after it and is not timed here)
+    const int lrc = launch(net, net->stream, d_in, n, d_pol, d_val, net->ev1);
     net->stamps_on = false;
     if (lrc) return -1;
-    HIPCHK(hipEventRecord(net->ev1, net->stream));
     for (int r = 0; r < d.role_count; ++r)
         HIPCHK(hipMemcpyAsync(policies[r], d_pol[r], (size_t)n * d.policy_dist_count[r] * 4, hipMemcpyDeviceToHost, net->stream));
     HIPCHK(hipMemcpyAsync(values, d_val, (size_t)n * d.num_values * 4, hipMemcpyDeviceToHost, net->stream));
@@ -791,6 +1178,68 @@ extern "C" int gz_net_set_output_logits(gz_net* net, int on) {
     if (!net) return fail("null net");
     std::lock_guard<std::mutex> wl(net->wmu);
     net->kp.logits = on ? 1 : 0;
+    if (net->shadow) net->shadow->net->kp.logits = net->kp.logits;
+    return 0;
+}
+
+extern "C" int gz_nn_compare_outputs(int device, int n, int roles, const int* policy_sizes, int num_values,
+                                     const float* const* pol_a, const float* val_a, const float* const* pol_b,
+                                     const float* val_b, gz_shadow_stats* out) {
+    if (!policy_sizes || !pol_a || !val_a || !pol_b || !val_b || !out) return fail("null argument");
+    if (n < 1 || roles < 1 || roles > GZ_MAX_ROLES || num_values < 1 || num_values > 4) return fail("compare: sizes out of range");
+    size_t row_f = num_values;
+    for (int r = 0; r < roles; ++r) {
+        if (policy_sizes[r] < 1 || !pol_a[r] || !pol_b[r]) return fail("compare: bad policy array");
+        row_f += policy_sizes[r];
+    }
+    HIPCHK(hipSetDevice(device));
+    // one allocation: a's arrays, b's arrays, the records, the block
+    const size_t side = ((size_t)n * row_f * sizeof(float) + 15) & ~(size_t)15;
+    const size_t recs = (size_t)n * sizeof(gzshadow::RowRecord);
+    char* mem = nullptr;
+    hipStream_t st = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t e = hipMalloc((void**)&mem, 2 * side + recs + sizeof(gz_shadow_stats));
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    gzshadow::CompareArgs ca{};
+    ca.nseg = 1;
+    ca.n = n;
+    ca.R = roles;
+    ca.V = num_values;
+    ca.rec = (gzshadow::RowRecord*)(mem + 2 * side);
+    gz_shadow_stats* d_acc = (gz_shadow_stats*)(mem + 2 * side + recs);
+    const char* cmp_err = nullptr;
+    if (e == hipSuccess) {
+        for (int sd = 0; sd < 2 && e == hipSuccess; ++sd) {
+            float* p = (float*)(mem + sd * side);
+            for (int r = 0; r < roles && e == hipSuccess; ++r) {
+                const size_t cnt = (size_t)n * policy_sizes[r];
+                e = hipMemcpyAsync(p, (sd ? pol_b : pol_a)[r], cnt * sizeof(float), hipMemcpyHostToDevice, st);
+                if (sd) ca.pol_b[r] = p; else ca.seg[0].pol[r] = p;
+                ca.P[r] = policy_sizes[r];
+                p += cnt;
+            }
+            if (e == hipSuccess) e = hipMemcpyAsync(p, sd ? val_b : val_a, (size_t)n * num_values * sizeof(float), hipMemcpyHostToDevice, st);
+            if (sd) ca.val_b = p; else ca.seg[0].val = p;
+        }
+        if (e == hipSuccess) e = hipEventRecord(e0, st);
+        if (e == hipSuccess) cmp_err = gzshadow::launch_compare(ca, 0, 1, d_acc, st);
+        if (e == hipSuccess && !cmp_err) e = hipEventRecord(e1, st);
+        if (e == hipSuccess && !cmp_err) e = hipMemcpyAsync(out, d_acc, sizeof(gz_shadow_stats), hipMemcpyDeviceToHost, st);
+        const hipError_t es = hipStreamSynchronize(st);   // (also after a failure: the uploads read the caller's arrays)
+        if (e == hipSuccess) e = es;
+        float ms = 0.f;
+        if (e == hipSuccess && !cmp_err) e = hipEventElapsedTime(&ms, e0, e1);
+        if (e == hipSuccess && !cmp_err) out->device_ms = ms;
+    }
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (st) (void)hipStreamDestroy(st);
+    if (mem) (void)hipFree(mem);
+    if (cmp_err) return fail(cmp_err);
+    if (e != hipSuccess) return fail(std::string("gz_nn_compare_outputs: ") + hipGetErrorString(e));
     return 0;
 }
 

@@ -32,10 +32,15 @@ def desc_from_conf(nn_model_conf, generation_descr=None):
 class HipModel(object):
     """Model object with the Keras inference surface the hot path uses."""
 
-    def __init__(self, desc, weights, device=0, precision="bf16"):
+    def __init__(self, desc, weights, device=0, precision="bf16", shadow=None):
+        """shadow: None, or (precision, every, max_rows) -- HipNet.enable_shadow before the weights
+        are set, e.g. ("fp32-ieee", 64, 256): the live check of this model's forwards against a
+        second arithmetic mode (self.net.shadow_stats())."""
         self.desc = desc
         self.weights = weights
         self.net = HipNet(desc, device, precision)
+        if shadow is not None:
+            self.net.enable_shadow(*shadow)
         self.net.set_weights(to_blob(weights))
 
     def predict_on_batch(self, X):

@@ -18,7 +18,9 @@ softmaxes saturate and a 5e-5 relative logit error moves individual probabilitie
 logits bound is the fp32-class criterion, the probability bounds state what that does to the outputs.
 tests/test_bench_shape_gpu.py, tests/test_nn_gpu.py::test_split_precision_against_fp32 and
 __graft_entry__.smoke() assert these constants (test_deep_config_bench_weights asserts each config's
-logits bound on its own, cfg2 included).
+logits bound on its own, cfg2 included).  These are offline figures on random nets; the error on the
+positions self-play visits with the weights actually loaded is what a net's shadow check reports
+live (HipNet.enable_shadow / shadow_stats, include/gzero_nn.h gz_net_shadow_enable).
 
 What the arithmetic is: bf16x3 ("split"; HipNet / bench.py --precision "bf16x3", the old name "fp32"
 is a deprecated alias) keeps ~16 significant bits per operand against IEEE fp32's 24, with fp32

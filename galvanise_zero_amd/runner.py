@@ -100,6 +100,11 @@ class SelfPlayRunner(object):
         self.lib.gz_runner_stats_get(self.handle, ctypes.byref(st))
         return st.as_dict()
 
+    def shadow_stats(self, reset=False):
+        """The shadow check's totals of this runner's net (HipNet.shadow_stats): safe while running.
+        A checked launch's shadow work is part of stats()["kernel_ms"]; "device_ms" here says how much."""
+        return self.net.shadow_stats(reset)
+
     def ordinal_stats(self):
         """Per-game costs by the game's ordinal within its slot (gz_ordinal_stats)."""
         st = _native.GzOrdinalStats()

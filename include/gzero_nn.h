@@ -208,6 +208,64 @@ int gz_net_heads_fused(const gz_net* net);
 
 const char* gz_nn_last_error(void);
 
+/* ---- shadow check: live forwards against a second arithmetic mode --------------------------------
+ * A net can carry a shadow: a second net of the same description and weights in another arithmetic
+ * mode (e.g. GZ_PRECISION_FP32 beside a GZ_PRECISION_SPLIT net).  Counting the net's forwards of at
+ * least one row from the enable, forward i is checked when i % every == 0 and both nets have
+ * weights: its first min(rows, max_rows) rows, in segment order, also run through the shadow on the
+ * caller's stream (same planes; outputs into a buffer of the shadow's), and two kernels
+ * (csrc/nn/shadow_compare.hip) compare the two sets of outputs and add to running totals on the
+ * device.  The net's own launches, outputs and trunk event are unchanged; gz_net_last_kernel_ms
+ * times the net's forward alone.  A caller timing the whole call on its stream (the runner's
+ * kernel_ms) sees a checked launch's shadow work: device_ms says how much.
+ * With GZ_NN_SHADOW=<precision>[:<every>[:<max_rows>]] in the environment (defaults 64 and 256)
+ * gz_net_create gives every net a shadow from birth and gz_net_destroy prints its totals to stderr;
+ * a malformed value fails gz_net_create with "GZ_NN_SHADOW: ...". */
+typedef struct gz_shadow_stats {
+    long checks;           /* launches compared */
+    long rows;             /* rows compared, the non-finite ones included */
+    long nonfinite_rows;   /* rows with a non-finite value in either net's policies or values:
+                              counted here and left out of every field below */
+    long policy_elems;     /* policy elements compared (denominator of the mean |dp|) */
+    long policy_rows;      /* (row, role) pairs compared (denominator of the mean KL) */
+    long value_elems;
+    double max_abs_dp, sum_abs_dp;     /* |p_net - p_shadow| over policy elements */
+    double max_row_kl, sum_row_kl;     /* KL(p_shadow || p_net) per (row, role), both clipped at 1e-30
+                                          (sum_i r_i log(r_i / g_i): slightly negative where the two rows'
+                                          sums differ; the maxima start from 0) */
+    long argmax_mismatch;              /* (row, role) pairs whose first-maximum index differs */
+    double max_abs_dv, sum_abs_dv;     /* values */
+    long worst_check, worst_row;       /* where max_abs_dp was seen: forward index of this net, row in it
+                                          (0, 0 while max_abs_dp is 0) */
+    double device_ms;                  /* shadow forward + comparison of all checks (HIP events) */
+} gz_shadow_stats;
+size_t gz_shadow_stats_sizeof(void);
+
+/* Gives `net` a shadow in arithmetic mode `precision` on the net's device.  Fails ("shadow: ...") when
+ * precision is the net's own mode, every < 1, max_rows < 1, the net already has a shadow, or
+ * gz_net_create refuses the geometry in that mode.  The shadow starts without weights (the net keeps
+ * no blob): checks begin with the first gz_net_set_weights / gz_net_set_weights_device after this
+ * call.  From then on both calls give both nets the blob -- if either refuses it ("shadow: ..." when
+ * it is the shadow), neither net's weights change -- and install both images in the critical
+ * section a launch takes, so a launch compares two nets of one generation (a live runner's roll
+ * included).  gz_net_set_output_logits reaches the shadow (KL fields then stay untouched);
+ * gz_net_destroy destroys it. */
+int gz_net_shadow_enable(gz_net* net, int precision, int every, int max_rows);
+int gz_net_shadow_disable(gz_net* net);
+/* Totals over the checks that have completed on the device, never a half-updated set; synchronises
+ * neither the device nor a stream (at most 8 checks are in flight: a launch that would queue a 9th
+ * first waits for the oldest).  reset != 0: later totals start from zero (checks still in flight
+ * are dropped).  The same sequence of checks gives the same bits (device_ms apart). */
+int gz_net_shadow_stats(gz_net* net, gz_shadow_stats* out, int reset);
+
+/* The comparison alone on `device`, host arrays in: a = the net ("got"), b = the shadow ("ref"),
+ * pol_x[r] float32 [n][policy_sizes[r]], val_x float32 [n][num_values].  *out = the totals of one
+ * check (checks 1, worst_check 0, device_ms the two kernels' time).  Outputs that are logits have no
+ * KL: compare them through a net in gz_net_set_output_logits mode. */
+int gz_nn_compare_outputs(int device, int n, int roles, const int* policy_sizes, int num_values,
+                          const float* const* pol_a, const float* val_a,
+                          const float* const* pol_b, const float* val_b, gz_shadow_stats* out);
+
 /* Diagnostics: with GZ_KERNEL_STAMPS set in the environment, gz_net_forward records per-workgroup
  * s_memtime stamps at phase boundaries; out8[0] = workgroups averaged, out8[1..4] = their mean
  * cycles of (input + initial conv, residual trunk, head 1x1 convs + features, fused dense heads)
