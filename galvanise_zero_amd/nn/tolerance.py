@@ -22,6 +22,15 @@ logits bound on its own, cfg2 included).  These are offline figures on random ne
 positions self-play visits with the weights actually loaded is what a net's shadow check reports
 live (HipNet.enable_shadow / shadow_stats, include/gzero_nn.h gz_net_shadow_enable).
 
+These constants come from the kernels they check (3x what was measured), so they bound what the
+kernels did on that day, not what a correct kernel may do.  What does not depend on any measurement
+is the exact suite (tests/exact_lattice.py, tests/test_nn_exact.py, tests/test_nn_exact_gpu.py;
+DESIGN 5): on nets whose every operand, product, sum and activation is representable in a mode's
+arithmetic, every mode, trunk family and kernel variant returns the float64 oracle's logits bit for
+bit -- it pins indices, taps, padding, channel order, the lo parts and their scales, the per-board
+exponents, with no tolerance at all.  It says nothing about rounding: the tolerance tests and the
+constants below remain the statement of accuracy on dense weights.
+
 What the arithmetic is: bf16x3 ("split"; HipNet / bench.py --precision "bf16x3", the old name "fp32"
 is a deprecated alias) keeps ~16 significant bits per operand against IEEE fp32's 24, with fp32
 accumulation and an fp32 residual stream.  It is fp32-CLASS, not fp32: on the headline cfg2 batch

@@ -1,0 +1,576 @@
+"""Exactly representable nets: weights and planes on which every forward mode must return the float64
+oracle's logits bit for bit (helper module of tests/test_nn_exact.py and tests/test_nn_exact_gpu.py;
+it holds no tests).
+
+If every operand, product, partial sum and activation of a forward is representable in the
+arithmetic a mode uses, every correctly rounded operation is exact in any order, fused or not, and a
+correct kernel returns the oracle's logits exactly.  lattice_weights / lattice_planes build such nets,
+check_representable asserts the conditions under which that is a theorem, expected_logits is the
+oracle (oracle/nn_ref.forward) snapped to the lattice, and faulty_logits applies a kernel-like slip
+to the oracle side so that the CPU suite can show the comparison would notice it.
+
+How the BN fold is made exact: galvanise_zero_amd/csrc/nn/weight_image.h fold_element computes
+scale = gamma / sqrt(fl32(var + 1e-3f)) in float32.  exact_vars() searches the float32 var for which
+fl32(var + 1e-3f) is exactly 1, 1/4 and 4, so scale is gamma, 2 gamma and gamma / 2 exactly.  The
+oracle adds 1e-3 to var in float64, which on those float32 vars is 1.3e-8 beside 1: a few 1e-9
+relative per BN, measured 1.2e-5 to 2e-4 lattice units on the two-block nets here and half a unit on
+boards scaled by 2^12 -- too much to snap.  So the oracle is given each var as the float64 v' with
+v' + 1e-3 == fl32(var + 1e-3f) (oracle_weights): the same net as the float32 fold defines, on which
+nn_ref.forward is exact, and expected_logits asserts both that the snap to the lattice moves nothing
+by more than 1e-5 units and that the oracle on the float32 vars as they are agrees within that drift.
+
+Left out, and why:
+  leaky_relu        0.03 is not dyadic: the negative side leaves every lattice
+  se_units > 0      the squeeze-excite gate is a sigmoid
+  pooling value head on boards whose position count is no power of two (13 x 13, 10 x 10): the
+                    trunk's channel mean is sum * fl32(1 / npos) (forward_kernel.h, "sm[r] * inv"),
+                    a reciprocal that is not a power of two; 8 x 8 (1 / 64) is exact
+These stay with the tolerance tests.
+"""
+import numpy as np
+
+from galvanise_zero_amd.nn.desc import weight_spec
+from galvanise_zero_amd.nn.weights import random_planes
+from oracle import nn_ref
+
+# significand bits of a conv operand (BN-folded weight, input) per arithmetic mode
+MODE_BITS = {"bf16": 8, "bf16-layered": 8, "bf16x3": 16, "bf16x3-layered": 16, "fp16x3-layered": 22, "fp32-ieee": 24}
+# three-part modes (hi hi + hi lo + lo hi, lo lo dropped): the bits of the hi part alone
+HI_BITS = {"bf16x3": 8, "bf16x3-layered": 8, "fp16x3-layered": 11}
+ACC_BITS = 24            # every sum is fp32
+GEMM_BITS, GEMM_HI = 16, 8   # policy_gemm_kernel: bf16 hi + lo of features and weights, in every mode that has it
+GEMM_MIN_P = 512         # gz_nn.hip: gemm_heads = ... && maxP >= 512 (and no fused heads)
+F16_MAX = 65504.0
+
+
+# ---- bit counting -------------------------------------------------------------------------------
+def _mant(a):
+    """(integer significands of 53 bits, exponents) of the nonzero elements of a (exact)."""
+    a = np.asarray(a, dtype=np.float64).reshape(-1)
+    a = np.abs(a[a != 0])
+    m, e = np.frexp(a)
+    return (m * 2.0 ** 53).astype(np.int64), e
+
+
+def _trailing(i):
+    return np.round(np.log2((i & -i).astype(np.float64))).astype(np.int64)   # (a power of two: exact)
+
+
+def sig_bits(a):
+    """The largest number of significant bits (first to last set bit) of any element; 0 for all zero."""
+    i, _ = _mant(a)
+    return int((53 - _trailing(i)).max()) if i.size else 0
+
+
+def lsb_exp(a):
+    """The smallest exponent of a lowest set bit: every element is a multiple of 2^lsb_exp(a).
+    None for an all-zero array."""
+    i, e = _mant(a)
+    return int((e - 53 + _trailing(i)).min()) if i.size else None
+
+
+def round_bits(a, bits):
+    """a rounded to `bits` significant bits, nearest even (what keeping a hi part alone does)."""
+    m, e = np.frexp(np.asarray(a, dtype=np.float64))
+    return np.ldexp(np.rint(np.ldexp(m, bits)), e - bits)
+
+
+def _emin(*es):
+    es = [e for e in es if e is not None]
+    return min(es) if es else None
+
+
+def _eadd(a, b):
+    return None if a is None or b is None else a + b
+
+
+# ---- the generator ------------------------------------------------------------------------------
+def exact_vars():
+    """{t: float32 var with fl32(var + 1e-3f) == t} for t = 1, 1/4, 4, found by search around t - 1e-3:
+    of the float32 that qualify, the one nearest t - 1e-3 (so the float64 oracle is nearest too)."""
+    eps = np.float32(1e-3)
+    out = {}
+    for t in (1.0, 0.25, 4.0):
+        v = np.float32(t - 1e-3)
+        cand = [v]
+        for _ in range(4):
+            cand = [np.nextafter(cand[0], np.float32(-1))] + cand + [np.nextafter(cand[-1], np.float32(9))]
+        ok = [c for c in cand if np.float32(c + eps) == np.float32(t)]
+        assert ok, t
+        out[t] = min(ok, key=lambda c: abs(float(c) - (t - 1e-3)))
+    return out
+
+
+# (gamma, fl32(var + eps)) pairs: scales 1/2 and 1 through all three vars
+_SCALE_PAIRS = {0.5: ((0.5, 1.0), (0.25, 0.25), (1.0, 4.0)), 1.0: ((1.0, 1.0), (0.5, 0.25), (2.0, 4.0))}
+WIDE_KINDS = ("initial_weights", "stream", "policy_dense")
+
+
+def _sparse(rng, shape, nnz, wmax, force_last):
+    """[kh, kw, cin, cout] (or [in, out]) with nnz signed integers of up to wmax per output, at random
+    places; force_last: outputs 0-3 keep one entry on the last input channel."""
+    cout = shape[-1]
+    cin = shape[-2]
+    places = int(np.prod(shape[:-1]))
+    nnz = min(nnz, places)
+    k = np.zeros((places, cout), dtype=np.float64)
+    for co in range(cout):
+        if force_last and co < 4 and cin > 1:
+            last = int(rng.integers(0, places // cin)) * cin + cin - 1
+            rest = rng.choice(places - 1, size=nnz - 1, replace=False)
+            at = np.concatenate([[last], rest + (rest >= last)])
+        else:
+            at = rng.choice(places, size=nnz, replace=False)
+        k[at, co] = rng.integers(1, wmax + 1, size=nnz) * rng.choice((-1, 1), size=nnz)
+    return k.reshape(shape)
+
+
+def _sparse_dense(rng, shape, nnz, lo, hi):
+    """[in, out] with about nnz entries of magnitude lo..hi per output (duplicates coincide)."""
+    k = np.zeros(shape, dtype=np.float64)
+    rows = rng.integers(0, shape[0], size=(nnz, shape[1]))
+    vals = rng.integers(lo, hi + 1, size=rows.shape) * rng.choice((-1, 1), size=rows.shape)
+    k[rows, np.arange(shape[1])[None, :]] = vals
+    return k
+
+
+def lattice_weights(desc, seed, *, nnz, wmax, wide=None):
+    """Weights in weight_spec order on which the forward is exact.
+
+    Conv kernels: sparse, nnz signed integers of up to wmax per 3 x 3 (initial) output channel at
+    random (tap, input channel) places; the heads' 1 x 1 convs, fp32 in every mode, read half of the
+    trunk's channels each (2 nnz with a wide policy Dense, whose features must stay narrow).  _var: one of
+    exact_vars(); _gamma: powers of two paired with the var so that the folded scale is 1/2 or 1;
+    _beta, _mean, conv biases, dense biases: integers in {-1, 0, 1}; dense kernels: sparse {-1, 0, 1}.
+
+    wide = {"kind": k, "bits": W, ...} makes one operand class use W significant bits (v1 nets):
+      "initial_weights"  the initial conv has one weight A per output channel, an odd integer of W
+                         bits with random bits all the way down (so that no hi + lo pair of a narrower
+                         mode holds it), under gamma = 2^-8 and mean = A - 32 - (channel mod 16): its
+                         output is (32 .. 47) / 256 where the plane is set, the wide part cancels in
+                         the fp32 epilogue, and a lost or mis-scaled lo part of the weight shows
+      "stream"           the initial BN's betas are such integers A of W bits, so the residual stream
+                         is W bits wide; every conv that reads the stream (res0_conv0, the heads'
+                         1 x 1 convs) is one +1 tap per output channel whose BN's mean is the A of the
+                         channel it reads less 32 (1,024 in the heads), which takes the wide part off
+                         again (needs value_bn and one residual block); integer lattice
+                         (W = 24: A = 2^23 + d with d < 16, so that |w x| + |bias| stays below 2^24;
+                         fp32's significand is one piece, so this uses its full width all the same)
+      "policy_dense"     the policy Dense kernels hold odd integers of W bits, two per output, on an
+                         integer lattice (gamma = 1 everywhere)
+    and wide = {"integer": True} alone only sets every gamma and var-sum to 1.
+
+    leaky_relu and se_units > 0 are refused (module docstring)."""
+    assert not desc.leaky_relu, "0.03 is not dyadic"
+    assert not desc.se_units, "the squeeze-excite gate is a sigmoid"
+    wide = dict(wide or {})
+    kind, W = wide.get("kind"), int(wide.get("bits", 0))
+    assert kind in (None,) + WIDE_KINDS, kind
+    integer = bool(wide.get("integer")) or kind in ("stream", "policy_dense")
+    if kind == "stream":
+        assert not desc.resnet_v2 and desc.residual_layers == 1 and desc.value_bn and not desc.conv_bias
+    if kind == "initial_weights":
+        assert not desc.resnet_v2 and not desc.conv_bias
+    rng = np.random.default_rng(seed)
+    var = exact_vars()
+    top = 2.0 ** (W - 1)
+
+    def wide_values(n, odd):
+        if W >= 24:
+            d = 2 * rng.integers(0, 8, size=n) + 1 if odd else rng.integers(3, 13, size=n)
+        else:
+            d = rng.integers(0, 2 ** (W - 2) - 2 ** (W - 5), size=n) * 2 + (1 if odd else rng.integers(0, 2, size=n))
+        return top + d
+    stream_base, last_conv = None, None
+    # what the BN named by a prefix does: "plain", "w0" (initial_weights), "beta" (stream's initial BN),
+    # ("shrink", offset) (a BN behind a conv that reads the wide stream)
+    special, single = {}, set()
+    if kind == "initial_weights":
+        special["initial_bn"] = "w0"
+        single.add("initial_conv")
+    if kind == "stream":
+        special["initial_bn"] = "beta"
+        special["res0_bn0"] = ("shrink", 32.0)
+        single.add("res0_conv0")
+        for r in range(desc.role_count):
+            special["policy%d_bn" % r] = ("shrink", 1024.0)
+            single.add("policy%d_conv" % r)
+        special["value_bn"] = ("shrink", 1024.0)
+        single.add("value_conv")
+    out, pairs = [], {}
+    for name, shape in weight_spec(desc):
+        n = shape[-1]
+        prefix = name.rsplit("_", 1)[0]
+        sp = special.get(prefix, "plain")
+        if len(shape) == 4:
+            head = shape[0] == 1 and shape[3] <= 2
+            if name in single:
+                k = _sparse(rng, shape, 1, 1, True)
+                k = np.abs(k)
+                if kind == "initial_weights":
+                    k = k * wide_values(n, True)
+            else:
+                # (the heads' convs are fp32 whatever the mode, so they can afford to read half of the
+                # stream each: a slip in any trunk channel then reaches a logit)
+                dense_head = head and kind != "policy_dense"
+                k = _sparse(rng, shape, shape[2] // 2 if dense_head else (2 * nnz if head else nnz), wmax, True)
+            a = last_conv = k
+        elif name.endswith("_gamma"):
+            if sp == "w0":
+                pairs[prefix] = [(2.0 ** -8, 1.0)] * n
+            elif integer or sp != "plain":
+                pairs[prefix] = [(1.0, 1.0)] * n
+            else:
+                sc = rng.choice((0.5, 1.0), size=n, p=(0.25, 0.75))
+                pairs[prefix] = [_SCALE_PAIRS[float(s)][int(rng.integers(0, 3))] for s in sc]
+            a = np.array([g for g, _ in pairs[prefix]])
+        elif name.endswith("_var"):
+            a = np.array([var[t] for _, t in pairs[prefix]], dtype=np.float32)
+        elif name.endswith("_beta"):
+            if sp == "beta":
+                a = stream_base = wide_values(n, False)
+            elif sp == "plain":
+                a = rng.integers(-1, 2, size=n)
+            else:
+                a = np.zeros(n)
+        elif name.endswith("_mean"):
+            if sp == "w0":
+                a = last_conv.sum(axis=(0, 1, 2)) - 32.0 - np.arange(n) % 16
+            elif isinstance(sp, tuple):      # the A of the stream channel each output reads
+                a = stream_base[np.argmax(last_conv.sum(axis=(0, 1)), axis=0)] - sp[1]
+            elif sp == "beta":
+                a = np.zeros(n)
+            else:
+                a = rng.integers(-1, 2, size=n)
+        elif len(shape) == 2:
+            if kind == "policy_dense" and name.startswith("policy"):
+                a = _sparse_dense(rng, shape, 2, 2 ** (W - 2), 2 ** (W - 1) - 1) * 2
+                a = a + np.sign(a)                     # odd, W bits
+            else:
+                a = _sparse_dense(rng, shape, 8, 1, 1)
+        else:                                          # conv biases (legacy), dense biases
+            a = rng.integers(-1, 2, size=n)
+        a = np.asarray(a, dtype=np.float64).reshape(shape)
+        assert np.array_equal(a.astype(np.float32).astype(np.float64), a), name
+        out.append((name, a.astype(np.float32)))
+    return out
+
+
+def zero_trunk_shifts(desc, weights):
+    """The same weights with every trunk BN's beta and mean and every trunk conv's bias zero: the
+    trunk is then positively homogeneous, so a board multiplied by a power of two keeps its
+    significand widths (the heads, fp32, keep their shifts)."""
+    out = []
+    for name, a in weights:
+        trunk = name.startswith("initial") or name.startswith("res")
+        if trunk and (name.endswith("_beta") or name.endswith("_mean") or name.endswith("_bias")):
+            a = np.zeros_like(a)
+        out.append((name, a))
+    return out
+
+
+def oracle_weights(weights):
+    """The same weights as the float64 oracle must read them: every _var as the float64 v' with
+    v' + 1e-3 == fl32(var + 1e-3f) exactly, so that nn_ref._bn's float64 var + 1e-3 is the number the
+    float32 fold (weight_image.h fold_element) divides by, and not 1.3e-8 beside it.  With the
+    float32 var itself the oracle is a few 1e-9 relative off the lattice, which on logits of 2^17
+    lattice units and more (boards scaled by 2^12) is no longer a fraction of a unit."""
+    out = []
+    for name, a in weights:
+        if name.endswith("_var"):
+            t = (a.astype(np.float32) + np.float32(nn_ref.EPS)).astype(np.float64)
+            v = t - nn_ref.EPS
+            for _ in range(8):
+                v = np.where(v + nn_ref.EPS < t, np.nextafter(v, np.inf), np.where(v + nn_ref.EPS > t, np.nextafter(v, -np.inf), v))
+            assert np.array_equal(v + nn_ref.EPS, t), name
+            a = v
+        out.append((name, a))
+    return out
+
+
+def lattice_planes(desc, n, seed, board_scale=None):
+    """random_planes' 0 / 1 boards; board_scale: one power of two per board."""
+    x = random_planes(desc, n, seed)
+    if board_scale is not None:
+        s = np.asarray(board_scale, dtype=np.float64)
+        assert s.shape == (n,) and np.all(s > 0) and sig_bits(s) == 1, s
+        x = (x * s[:, None, None, None]).astype(np.float32)
+    return x
+
+
+# ---- the forward, restated on the oracle's own pieces, with a tap on every conv ---------------------
+def _fold64(w, conv, bn):
+    """(scale, bias) of the BN behind a conv as float64 arrays, scale from fold_element's float32
+    formula (weight_image.h): the exact scale when var is one of exact_vars()."""
+    cb = w.get(conv + "_bias") if conv else None
+    if bn is None:
+        n = w[conv].shape[3]
+        return np.ones(n), (cb.astype(np.float64) if cb is not None else np.zeros(n))
+    g, b, m, v = (w[bn + s].astype(np.float32) for s in ("_gamma", "_beta", "_mean", "_var"))
+    sc32 = g / np.sqrt(v + np.float32(nn_ref.EPS))
+    sc = sc32.astype(np.float64)
+    assert sig_bits(sc) <= 1, (bn, "the folded scale is no power of two")
+    bi = b.astype(np.float64) + ((cb.astype(np.float64) if cb is not None else 0.0) - m.astype(np.float64)) * sc
+    bi32 = (b + (cb.astype(np.float32) - m) * sc32) if cb is not None else (b - m * sc32)
+    assert np.array_equal(bi32.astype(np.float64), bi), (bn, "the float32 fold of the bias is not exact")
+    return sc, bi
+
+
+def _conv(x, k, wrap=False):
+    """nn_ref._conv_same; wrap: the left padding column holds the board's last column (what reading
+    position p - 1 across a row's end does) instead of zeros."""
+    if not wrap:
+        return nn_ref._conv_same(x, k)
+    kh, kw = k.shape[0], k.shape[1]
+    assert kw == 3
+    N, H, Wd, _ = x.shape
+    xp = np.pad(x, ((0, 0), (kh // 2, kh // 2), (1, 1), (0, 0)))
+    xp[:, :, 0, :] = xp[:, :, Wd, :]
+    out = np.zeros((N, H, Wd, k.shape[3]))
+    for dy in range(kh):
+        for dx in range(kw):
+            out += xp[:, dy:dy + H, dx:dx + Wd, :] @ k[dy, dx].astype(np.float64)
+    return out
+
+
+def _forward(desc, weights, planes, tap=None, hooks=None):
+    """nn_ref.forward(..., logits=True) restated with nn_ref's pieces (_conv_same, _bn, _act).
+
+    hooks: {conv name: f(inp, k) -> (inp, k, wrap)} alters one conv's operands (faulty_logits).
+    tap(kind, name, inp, k, bn, skip): called for every conv ("trunk" / "head"), every v2
+    pre-activation ("affine": k is None), every Dense ("dense" / "gemm": bn is the bias array) and
+    the pooled mean ("pool").  Returns (logits [policy.., value] float64, final trunk activations)."""
+    w = dict(oracle_weights(weights))
+    hooks = hooks or {}
+    tap = tap or (lambda *a: None)
+    assert not desc.leaky_relu and not desc.se_units
+    act = lambda t: nn_ref._act(t, False)
+
+    def conv(x, name, bn, kind, skip=None):
+        k = w[name].astype(np.float64)
+        wrap = False
+        if name in hooks:
+            x, k, wrap = hooks[name](x, k)
+        tap(kind, name, x, k, bn, skip)
+        y = _conv(x, k, wrap)
+        if desc.conv_bias:
+            y = y + w[name + "_bias"].astype(np.float64)
+        return nn_ref._bn(y, w, bn) if bn else y
+
+    def dense(x, name, bias, kind="dense"):
+        k = w[name].astype(np.float64)
+        tap(kind, name, x, k, w[bias].astype(np.float64), None)
+        return x @ k + w[bias].astype(np.float64)
+
+    x = np.transpose(planes.astype(np.float64), (0, 2, 3, 1))
+    v2 = desc.resnet_v2
+    has_bn0 = not v2 or desc.initial_bn
+    x = conv(x, "initial_conv", "initial_bn" if has_bn0 else None, "trunk")
+    if has_bn0:
+        x = act(x)
+    layers = [x]
+    for i in range(desc.residual_layers):
+        t = x
+        if v2:
+            tap("affine", "res%d_bn1" % i, x, None, "res%d_bn1" % i, None)
+            y = act(conv(act(nn_ref._bn(x, w, "res%d_bn1" % i)), "res%d_conv1" % i, "res%d_bn2" % i, "trunk"))
+            x = t + conv(y, "res%d_conv2" % i, None, "trunk", skip=t)
+        else:
+            y = act(conv(x, "res%d_conv0" % i, "res%d_bn0" % i, "trunk"))
+            x = act(t + conv(y, "res%d_conv1" % i, "res%d_bn1" % i, "trunk", skip=t))
+        layers.append(x)
+    gemm = max(desc.policy_dist_count) >= GEMM_MIN_P
+    outs = []
+    for r in range(desc.role_count):
+        h = act(conv(x, "policy%d_conv" % r, "policy%d_bn" % r, "head"))
+        outs.append(dense(nn_ref._flatten(h, desc.flatten_nchw), "policy%d_dense" % r, "policy%d_bias" % r,
+                          "gemm" if gemm else "dense"))
+    if desc.concat_all_layers:
+        flat = np.concatenate([nn_ref._flatten(act(conv(l, "value%d_conv" % j, "value%d_bn" % j, "head")), desc.flatten_nchw)
+                               for j, l in enumerate(layers)], axis=1)
+    else:
+        flat = nn_ref._flatten(act(conv(x, "value_conv", "value_bn" if desc.value_bn else None, "head")), desc.flatten_nchw)
+        if desc.global_pooling_value:
+            tap("pool", "trunk", x, None, None, None)
+            flat = np.concatenate([x.mean(axis=(1, 2)), flat], axis=1)
+    hid = act(dense(flat, "value_hidden", "value_hidden_bias"))
+    outs.append(dense(hid, "value_dense", "value_bias"))
+    return outs, x
+
+
+def lattice_exponent(desc, weights, planes):
+    """e with every logit a multiple of 2^e, from the exponents of the weights' and the planes' own
+    lowest set bits alone (no activation is looked at): through a conv and its BN
+    e_out = min(e_in + e(folded weights), e(folded bias)), through an add the smaller of the two."""
+    w = dict(weights)
+
+    def conv(e, name, bn):
+        sc, bi = _fold64(w, name, bn)
+        return _emin(_eadd(e, lsb_exp(w[name].astype(np.float64) * sc)), lsb_exp(bi))
+
+    def dense(e, name, bias):
+        return _emin(_eadd(e, lsb_exp(w[name])), lsb_exp(w[bias]))
+
+    v2 = desc.resnet_v2
+    e = conv(lsb_exp(planes), "initial_conv", "initial_bn" if (not v2 or desc.initial_bn) else None)
+    layers = [e]
+    for i in range(desc.residual_layers):
+        if v2:
+            sc, bi = _fold64(w, None, "res%d_bn1" % i)
+            y = conv(_emin(_eadd(e, lsb_exp(sc)), lsb_exp(bi)), "res%d_conv1" % i, "res%d_bn2" % i)
+            y = conv(y, "res%d_conv2" % i, None)
+        else:
+            y = conv(conv(e, "res%d_conv0" % i, "res%d_bn0" % i), "res%d_conv1" % i, "res%d_bn1" % i)
+        e = _emin(e, y)
+        layers.append(e)
+    outs = [dense(conv(e, "policy%d_conv" % r, "policy%d_bn" % r), "policy%d_dense" % r, "policy%d_bias" % r)
+            for r in range(desc.role_count)]
+    if desc.concat_all_layers:
+        f = _emin(*[conv(l, "value%d_conv" % j, "value%d_bn" % j) for j, l in enumerate(layers)])
+    else:
+        f = conv(e, "value_conv", "value_bn" if desc.value_bn else None)
+        if desc.global_pooling_value:
+            assert sig_bits(float(desc.hw)) == 1, "the pooled mean is dyadic only where the position count is a power of two"
+            f = _emin(f, _eadd(e, -int(np.log2(desc.hw))))
+    outs.append(dense(dense(f, "value_hidden", "value_hidden_bias"), "value_dense", "value_bias"))
+    e = _emin(*outs)
+    assert e is not None
+    return e
+
+
+# the float32 var beside the float64 v' of oracle_weights: |var + 1e-3 - t| / t <= 2^-25 (the rounding
+# of the float32 sum) + 4.8e-11 / 0.25 (1e-3f against 1e-3), half of it on the scale, per BN
+ORACLE_VAR_DRIFT = 0.5 * (2.0 ** -25 + 2e-10)
+
+
+def expected_logits(desc, weights, planes):
+    """oracle/nn_ref.forward(oracle_weights(weights), logits=True) snapped to the lattice unit
+    2^lattice_exponent; the snap must move nothing by more than 1e-5 units.  Also asserts that the
+    oracle on the float32 vars as they are is the same net: within the drift of its var + 1e-3 over
+    the deepest chain of BNs, relative to the largest logit.  [policy_0, .., value] float64."""
+    unit = 2.0 ** lattice_exponent(desc, weights, planes)
+    plain = nn_ref.forward(desc, weights, planes, logits=True)
+    depth = 2 * desc.residual_layers + 2
+    out = []
+    for z, zp in zip(nn_ref.forward(desc, oracle_weights(weights), planes, logits=True), plain):
+        q = np.rint(z / unit)
+        moved = float(np.abs(z / unit - q).max())
+        assert moved <= 1e-5, ("the oracle is %.3g units of %g off the lattice" % (moved, unit))
+        out.append(q * unit)
+        assert np.abs(zp - z).max() <= 8 * depth * ORACLE_VAR_DRIFT * np.abs(z).max(), (np.abs(zp - z).max(), np.abs(z).max())
+    return out
+
+
+def trunk_alive(desc, weights, planes):
+    """The fraction of the final trunk activations that are nonzero."""
+    _, x = _forward(desc, weights, planes)
+    return float(np.count_nonzero(x)) / x.size
+
+
+# ---- the conditions -----------------------------------------------------------------------------
+def check_representable(desc, weights, planes, mode):
+    """Asserts the conditions under which the forward of `mode` on these weights and planes is exact
+    (walking the net with the oracle's own pieces, v1 and v2):
+
+    * every trunk conv's BN-folded weights and inputs have at most MODE_BITS[mode] significant bits;
+    * three-part modes drop lo x lo: per conv, every folded weight or every input fits the hi part
+      (HI_BITS[mode]);
+    * per output, sum |w x| + |bias| + |skip| < 2^24 units of the output's lattice, so fp32 partial
+      sums are exact in any order, grouping or fusion; the same for the v2 pre-activations;
+    * the heads' 1 x 1 convs and the Denses are fp32 from the fp32 stream: 24 bits, same sums; the
+      policy Dense where policy_gemm_kernel runs it (largest policy >= 512 outside fp32-ieee and
+      fp16x3-layered; on nets with fused heads this is stricter than needed): 16 bits, one side
+      within 8;
+    * fp16x3-layered: folded weights within fp16's range and clear of its subnormals; within one
+      board the largest and the smallest nonzero |input| of a conv less than 2^20 apart, so that
+      with the board's exponent (layered_forward.h board_exponent: the largest lies in [2^14, 2^15))
+      hi parts and the scaled lo parts stay clear of fp16's subnormals;
+    * a pooling value head only where the position count is a power of two.
+    """
+    bits, hi = MODE_BITS[mode], HI_BITS.get(mode)
+    w = dict(weights)
+    gemm_mode = mode not in ("fp32-ieee", "fp16x3-layered")
+
+    def sums(name, inp, kf, bi, skip, conv):
+        a = np.abs(inp)
+        s = (nn_ref._conv_same(a, np.abs(kf)) if conv else a @ np.abs(kf)) + np.abs(bi)
+        if skip is not None:
+            s = s + np.abs(skip)
+        ek, eb = lsb_exp(kf), lsb_exp(bi)
+        for b in range(inp.shape[0]):      # a board's sums are its own: so is its lattice
+            e = _emin(_eadd(lsb_exp(inp[b]), ek), eb, lsb_exp(skip[b]) if skip is not None else None)
+            if e is not None:
+                assert s[b].max() < 2.0 ** (ACC_BITS + e), (mode, name, b, "sum of |terms| %.6g reaches 2^24 units of %g" % (s[b].max(), 2.0 ** e))
+
+    def two_sided(name, what, kf, inp, full, part):
+        bw, bx = sig_bits(kf), sig_bits(inp)
+        assert bw <= full, (mode, name, "%s weights need %d bits, the mode has %d" % (what, bw, full))
+        assert bx <= full, (mode, name, "%s inputs need %d bits, the mode has %d" % (what, bx, full))
+        if part is not None:
+            assert bw <= part or bx <= part, (mode, name, "lo x lo is dropped: weights %d bits, inputs %d, hi part %d" % (bw, bx, part))
+
+    def tap(kind, name, inp, k, bn, skip):
+        if kind == "pool":
+            assert sig_bits(float(desc.hw)) == 1, (name, "1 / %d is not a power of two" % desc.hw)
+            s = np.abs(inp).sum(axis=(1, 2))
+            e = lsb_exp(inp)
+            assert e is None or s.max() < 2.0 ** (ACC_BITS + e), (mode, "pooled sum")
+            return
+        if kind == "affine":
+            sc, bi = _fold64(w, None, bn)
+            e = _emin(_eadd(lsb_exp(inp), lsb_exp(sc)), lsb_exp(bi))
+            s = np.abs(inp) * np.abs(sc) + np.abs(bi)
+            assert e is None or s.max() < 2.0 ** (ACC_BITS + e), (mode, name, "pre-activation")
+            return
+        if kind in ("dense", "gemm"):
+            if kind == "gemm" and gemm_mode:
+                two_sided(name, "policy GEMM", k, inp, GEMM_BITS, GEMM_HI)
+            else:
+                two_sided(name, "Dense", k, inp, ACC_BITS, None)
+            sums(name, inp, k, bn, None, False)
+            return
+        sc, bi = _fold64(w, name, bn)
+        kf = k * sc
+        assert np.array_equal((k.astype(np.float32) * sc.astype(np.float32)).astype(np.float64), kf), (name, "float32 fold")
+        if kind == "head":
+            two_sided(name, "head conv", kf, inp, ACC_BITS, None)
+        else:
+            two_sided(name, "conv", kf, inp, bits, hi)
+            if mode == "fp16x3-layered":
+                nz = np.abs(kf[kf != 0])
+                assert nz.max() <= F16_MAX and lsb_exp(kf) >= -14, (name, "folded weights against fp16's range")
+                a = np.abs(inp).reshape(inp.shape[0], -1)
+                for b in range(a.shape[0]):
+                    pos = a[b][a[b] > 0]
+                    assert pos.size == 0 or pos.max() / pos.min() < 2.0 ** 20, (name, b, "input range within the board")
+        sums(name, inp, kf, bi, skip, True)
+
+    _forward(desc, weights, planes, tap=tap)
+
+
+# ---- faults, on the oracle side only ------------------------------------------------------------------
+FAULTS = ("tap_swap", "wrap_pad", "channel_swap", "drop_last_channel", "lo_weights", "lo_inputs")
+
+
+def faulty_logits(desc, weights, planes, fault, conv, bits=8):
+    """The logits of a forward whose conv `conv` slips the way a wrong kernel or packer would:
+    two taps swapped, wrap-around for zero padding along the left border, two input channels
+    swapped, the last input channel dropped, the weights' / the inputs' lo part lost (the operand
+    rounded to `bits` significant bits)."""
+    def hook(inp, k):
+        k = k.copy()
+        if fault == "tap_swap":
+            k[[0, k.shape[0] - 1], [0, k.shape[1] // 2]] = k[[k.shape[0] - 1, 0], [k.shape[1] // 2, 0]]
+        elif fault == "channel_swap":
+            a, b = int(np.argmax((k != 0).sum(axis=(0, 1, 3))[:-1])), k.shape[2] - 1   # the busiest and the last
+            k[:, :, [a, b]] = k[:, :, [b, a]]
+        elif fault == "drop_last_channel":
+            k[:, :, -1] = 0.0
+        elif fault == "lo_weights":
+            k = round_bits(k, bits)
+        elif fault == "lo_inputs":
+            inp = round_bits(inp, bits)
+        else:
+            assert fault == "wrap_pad", fault
+        return inp, k, fault == "wrap_pad"
+    return _forward(desc, weights, planes, hooks={conv: hook})[0]

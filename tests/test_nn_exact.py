@@ -1,0 +1,197 @@
+"""CPU side of the exact suite (tests/test_nn_exact_gpu.py): every net of that file meets, for every
+mode it is run in, the conditions under which exactness is a theorem (exact_lattice.
+check_representable); the nets are alive; and the comparison would notice a wrong kernel -- each
+kernel-like slip, applied to the oracle side alone, moves at least one expected logit.  No GPU."""
+import numpy as np
+import pytest
+
+import exact_lattice as xl
+from galvanise_zero_amd.nn.desc import NetDesc
+from oracle import nn_ref
+from test_nn_exact_gpu import ALL, CASES, CHUNKED, LARGE_ROWS, PROBABILITY, SCALES, build
+
+FAMILIES = {c.family: name for name, c in CASES.items() if c.family}
+GEOMETRY_FAULTS = ("tap_swap", "wrap_pad", "channel_swap", "drop_last_channel")
+
+
+def _last_residual_conv(desc):
+    return "res%d_conv%d" % (desc.residual_layers - 1, 2 if desc.resnet_v2 else 1)
+
+
+def _differs(a, b):
+    return any(not np.array_equal(p, q) for p, q in zip(a, b))
+
+
+def test_exact_vars():
+    """The three vars are found by search, and the float32 fold's var + 1e-3f is 1, 1/4 and 4 on them."""
+    v = xl.exact_vars()
+    assert sorted(v) == [0.25, 1.0, 4.0]
+    for t, var in v.items():
+        assert var.dtype == np.float32 and np.float32(var + np.float32(1e-3)) == np.float32(t)
+        assert np.float32(1.0) / np.sqrt(np.float32(var + np.float32(1e-3))) == np.float32(t ** -0.5)
+    assert abs(float(v[1.0]) - 0.999) < 1e-7
+
+
+def test_generator_refuses_inexact_flags():
+    for flag in (dict(leaky_relu=True), dict(resnet_v2=True, se_units=42)):
+        with pytest.raises(AssertionError):
+            xl.lattice_weights(NetDesc(5, 8, 8, 128, 1, [155, 155], **flag), 1, nnz=2, wmax=1)
+
+
+def test_generator_covers_the_lattice():
+    """Sparse integer convs, all three vars, several powers of two as gamma, integer shifts."""
+    desc, w, _, _ = build("8x8_f128_b2")
+    w = dict(w)
+    k = w["res1_conv0"]
+    assert set(np.unique(k)) == {-1.0, 0.0, 1.0} and np.all((k != 0).sum(axis=(0, 1, 2)) == 2)
+    assert np.all((w["policy0_conv"] != 0).sum(axis=(0, 1, 2)) == 64)      # the heads read half of the trunk each
+    vars_ = np.unique(np.concatenate([a for n, a in w.items() if n.endswith("_var")]))
+    assert set(vars_) == set(float(v) for v in xl.exact_vars().values())
+    gammas = np.unique(np.concatenate([a for n, a in w.items() if n.endswith("_gamma")]))
+    assert len(gammas) >= 3 and all(xl.sig_bits(g) == 1 for g in gammas)
+    for suffix in ("_beta", "_mean", "policy0_bias", "value_hidden_bias"):
+        vals = np.unique(np.concatenate([a for n, a in w.items() if n.endswith(suffix)]))
+        assert set(vals) == {-1.0, 0.0, 1.0}, suffix
+    assert set(np.unique(w["policy0_dense"])) == {-1.0, 0.0, 1.0}
+
+
+@pytest.mark.parametrize("name", ["8x8_f128_b2", "v2_8x8_f128_b2_pool", "v2_13x13_f256_b2_concat", "6x9_legacy_f40_b2",
+                                  "v2_10x10_f256_b1_bare"])
+def test_walk_is_the_oracle(name):
+    """exact_lattice._forward, which the conditions and the faults walk, is nn_ref.forward."""
+    desc, w, x, expected = build(name)
+    ours, _ = xl._forward(desc, w, x)
+    for a, b, e in zip(ours, nn_ref.forward(desc, xl.oracle_weights(w), x, logits=True), expected):
+        assert np.array_equal(a, b) and np.array_equal(a, e)
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_conditions(name):
+    """check_representable holds for every mode the GPU file runs the net in; where the case claims
+    every mode whose conditions hold, it fails for each mode left out."""
+    c = CASES[name]
+    desc, w, x, _ = build(name)
+    for mode in c.modes:
+        xl.check_representable(desc, w, x, mode)
+    if c.exhaustive:
+        for mode in set(ALL) - set(c.modes):
+            with pytest.raises(AssertionError):
+                xl.check_representable(desc, w, x, mode)
+
+
+@pytest.mark.parametrize("rows,names", [(5, ("8x8_f128_b2", CHUNKED)), (LARGE_ROWS, ("8x8_f128_b2",))])
+def test_conditions_at_other_row_counts(rows, names):
+    for name in names:
+        desc, w, x, _ = build(name, rows)
+        for mode in CASES[name].modes:
+            xl.check_representable(desc, w, x, mode)
+
+
+def test_wide_cases_use_the_width():
+    """The wide nets put the stated number of bits where they say: the initial conv's folded weights,
+    the residual convs' inputs, the policy Dense's weights and features."""
+    seen = {}
+
+    def tap(kind, name, inp, k, bn, skip):
+        seen[name] = (xl.sig_bits(inp), xl.sig_bits(k) if k is not None else 0)
+    for bits in (16, 22, 24):
+        desc, w, x, _ = build("wide_w0_%d" % bits)
+        xl._forward(desc, w, x, tap=tap)
+        assert seen["initial_conv"][1] == bits
+        desc, w, x, _ = build("wide_stream_%d" % bits)
+        xl._forward(desc, w, x, tap=tap)
+        assert seen["res0_conv0"][0] == bits and seen["policy0_conv"][0] >= bits - 1
+    desc, w, x, _ = build("gemm_wide_features")
+    xl._forward(desc, w, x, tap=tap)
+    assert 8 < seen["policy0_dense"][0] <= 16 and seen["policy0_dense"][1] == 1
+    desc, w, x, _ = build("gemm_wide_weights")
+    xl._forward(desc, w, x, tap=tap)
+    assert seen["policy0_dense"][0] <= 8 and seen["policy0_dense"][1] == 16
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_liveness(name):
+    """Conditions on the inputs, on the oracle alone: at least 30 % of the final trunk is nonzero,
+    every policy role's expected logits take at least 32 values, the value logits are not all equal."""
+    desc, w, x, expected = build(name)
+    assert desc.residual_layers < 6
+    assert xl.trunk_alive(desc, w, x) >= 0.30
+    for z in expected[:-1]:
+        assert len(np.unique(z)) >= 32
+    assert len(np.unique(expected[-1])) > 1
+
+
+@pytest.mark.parametrize("fault", GEOMETRY_FAULTS)
+@pytest.mark.parametrize("family", sorted(FAMILIES))
+def test_fault_is_seen(family, fault):
+    """Two taps swapped, wrap-around padding along one border, two input channels swapped, the last
+    input channel dropped (F = 96 padded to 128 among the families), in the last residual conv."""
+    desc, w, x, expected = build(FAMILIES[family])
+    assert _differs(xl.faulty_logits(desc, w, x, fault, _last_residual_conv(desc)), expected)
+
+
+@pytest.mark.parametrize("name,mode", [(name, mode) for name, c in CASES.items() if c.wide and c.wide.get("kind") in
+                                       ("initial_weights", "stream") for mode in c.modes])
+def test_lost_lo_part_is_seen(name, mode):
+    """Wide cases: the operand of the wide conv rounded to the mode's hi format (fp32-ieee has no lo
+    part: there, a rounding to bf16x3's 16 bits where the net is wider than that, else to 8)."""
+    desc, w, x, expected = build(name)
+    bits = xl.HI_BITS.get(mode, 16 if CASES[name].wide["bits"] > 16 else 8)
+    fault, conv = ("lo_weights", "initial_conv") if CASES[name].wide["kind"] == "initial_weights" else ("lo_inputs", "res0_conv0")
+    assert _differs(xl.faulty_logits(desc, w, x, fault, conv, bits=bits), expected)
+
+
+@pytest.mark.parametrize("name,kind", [("gemm_wide_features", "inputs"), ("gemm_wide_weights", "weights")])
+def test_lost_lo_part_of_the_policy_gemm_is_seen(name, kind):
+    desc, w, x, expected = build(name)
+    w2 = [(n, xl.round_bits(a, 8).astype(np.float32) if (kind == "weights" and n == "policy1_dense") else a) for n, a in w]
+    if kind == "weights":
+        got = xl._forward(desc, w2, x)[0]
+    else:
+        seen = {}
+
+        def tap(k, n, inp, *rest):
+            if n == "policy1_dense":
+                seen["z"] = xl.round_bits(inp, 8) @ dict(w)["policy1_dense"].astype(np.float64) + dict(w)["policy1_bias"]
+        xl._forward(desc, w, x, tap=tap)
+        got = list(expected)
+        got[1] = seen["z"]
+    assert _differs(got, expected)
+
+
+@pytest.mark.parametrize("name", ["8x8_scaled", "8x8_scaled_permuted"])
+def test_neighbours_scale_is_seen(name):
+    """One board of a scaled launch given its neighbour's scale."""
+    desc, w, x, expected = build(name)
+    for b in range(x.shape[0]):
+        nb = (b + 1) % x.shape[0]
+        bad = x.copy()
+        bad[b] = x[b] * np.float32(np.abs(x[nb]).max() / np.abs(x[b]).max())
+        got = nn_ref.forward(desc, xl.oracle_weights(w), bad, logits=True)
+        assert all(not np.array_equal(g[b], e[b]) for g, e in zip(got, expected)), b
+
+
+def test_scaled_boards():
+    """The scaled case holds the four scales, the permuted case the same boards in another order, and
+    its expected logits are the first case's rows in that order."""
+    _, _, x, expected = build("8x8_scaled")
+    _, _, xp, expected_p = build("8x8_scaled_permuted")
+    assert tuple(float(np.abs(b).max()) for b in x) == SCALES
+    order = list(CASES["8x8_scaled_permuted"].order)
+    assert np.array_equal(xp, x[order])
+    for e, ep in zip(expected, expected_p):
+        assert np.array_equal(ep, e[order])
+
+
+def test_every_mode_and_family_is_run():
+    """Every arithmetic mode of the README, every kernel family, and a probability-mode forward per
+    mode are in the GPU file's parametrisation."""
+    import os
+    readme = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "README.md")).read()
+    section = readme.split("## Arithmetic modes")[1].split("\n## ")[0]
+    run = {m for c in CASES.values() for m in c.modes}
+    assert run == set(ALL) == set(xl.MODE_BITS)
+    for mode in ALL:
+        assert '"%s"' % mode in section or "`\"%s\"`" % mode in section, mode
+    assert {m for _, m in PROBABILITY} == set(ALL)
+    assert len(FAMILIES) >= 9
