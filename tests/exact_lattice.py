@@ -19,12 +19,29 @@ v' + 1e-3 == fl32(var + 1e-3f) (oracle_weights): the same net as the float32 fol
 nn_ref.forward is exact, and expected_logits asserts both that the snap to the lattice moves nothing
 by more than 1e-5 units and that the oracle on the float32 vars as they are agrees within that drift.
 
+Squeeze-excite is in, under saturation conditions.  The gate is a sigmoid, but a float32
+1.f / (1.f + exp(-z)) is exact at three points: 1 for z >= 17.4, 0 for z <= -88.8, 1/2 at z = 0 (ZSAT
+below).  lattice_se_weights builds nets whose every gate is one of the three -- a +-1 compress matrix,
+a gating matrix with at most one +-K per channel, K the smallest power of two that puts every nonzero
+z at |z| >= 256 -- and u * 0, u * 1/2, u * 1 keep the stream on the lattice (one step lower per block).
+_forward computes such gates as classes and refuses anything else; check_representable adds the
+conditions under which the device's gates are those classes: on boards whose position count is a
+power of two the whole gate path (sums, means, both Denses) is exact in any order, and the nets hold
+a hidden unit that is exactly 0 from nonzero terms, so that a mean off by one count flips a gate; on
+the other boards the mean is sum * fl32(1 / npos), and every hidden unit a gate reads must clear
+twice the float32 error bound of its sum (se_fragile_units; units that do not are muted).  The gates
+take all three values and differ from board to board and from channel to channel (se_liveness), so a
+neighbour's gates, gates off by a lane group or a co tile, another block's matrices, a dropped unit,
+a missing relu or a gate applied after the add each move a logit (faulty_se_logits).
+
 Left out, and why:
   leaky_relu        0.03 is not dyadic: the negative side leaves every lattice
-  se_units > 0      the squeeze-excite gate is a sigmoid
+  se_units > 0 without saturating gates (lattice_weights refuses it unless given se=...)
   pooling value head on boards whose position count is no power of two (13 x 13, 10 x 10): the
                     trunk's channel mean is sum * fl32(1 / npos) (forward_kernel.h, "sm[r] * inv"),
                     a reciprocal that is not a power of two; 8 x 8 (1 / 64) is exact
+  small errors in the scale of the squeeze-excite mean on boards whose position count is no power
+                    of two: a saturated gate cannot see them, by construction
 These stay with the tolerance tests.
 """
 import numpy as np
@@ -134,7 +151,49 @@ def _sparse_dense(rng, shape, nnz, lo, hi):
     return k
 
 
-def lattice_weights(desc, seed, *, nnz, wmax, wide=None):
+SE_PER_UNIT = 16         # entries of a compress unit: half +1, half -1
+SE_READS = 0.75          # the share of the channels whose gate reads a unit (the others: a zero column, gate 1/2)
+
+
+def _se_compress(rng, shape, twin):
+    """[F, S]: per unit SE_PER_UNIT entries at random channels, half +1 and half -1.  twin = (c1, c2,
+    unit): that unit reads +c1 - c2 alone, two channels whose conv2 kernels are the same, so that
+    its pre-activation is exactly 0 from nonzero terms, and one count too few in either mean shows."""
+    F, S = shape
+    n = min(SE_PER_UNIT, F // 2 * 2)
+    a = np.zeros(shape)
+    for j in range(S):
+        at = rng.choice(F, size=n, replace=False)
+        a[at[:n // 2], j], a[at[n // 2:], j] = 1.0, -1.0
+    if twin:
+        a[:, twin[2]] = 0.0
+        a[twin[0], twin[2]], a[twin[1], twin[2]] = 1.0, -1.0
+    return a
+
+
+def _se_gating(rng, shape, K, mute, twin):
+    """[S, F]: at most one entry +-K per channel, about a quarter of the channels none; two channels
+    are made to read unit S - 1 and (S > 64) a unit >= 64, a third the twin unit (_se_compress).
+    mute: units whose row is zeroed.  (The draws do not depend on K or mute.)"""
+    S, F = shape
+    reads = rng.random(F) < SE_READS
+    units = rng.integers(0, S, size=F)
+    signs = rng.choice((-1.0, 1.0), size=F)
+    ca, cb, cc = rng.choice(F, size=3, replace=False)
+    high = int(rng.integers(min(64, S - 1), S))
+    reads[ca], units[ca] = True, S - 1
+    if S > 64:
+        reads[cb], units[cb] = True, high
+    if twin:
+        reads[cc], units[cc] = True, twin[2]
+    a = np.zeros(shape)
+    c = np.nonzero(reads)[0]
+    a[units[c], c] = signs[c] * K
+    a[sorted(mute)] = 0.0
+    return a
+
+
+def lattice_weights(desc, seed, *, nnz, wmax, wide=None, se=None):
     """Weights in weight_spec order on which the forward is exact.
 
     Conv kernels: sparse, nnz signed integers of up to wmax per 3 x 3 (initial) output channel at
@@ -160,9 +219,17 @@ def lattice_weights(desc, seed, *, nnz, wmax, wide=None):
                          integer lattice (gamma = 1 everywhere)
     and wide = {"integer": True} alone only sets every gamma and var-sum to 1.
 
-    leaky_relu and se_units > 0 are refused (module docstring)."""
+    se = {"K": K, "mute": {(block, unit), ..}} is what a squeeze-excite net needs (lattice_se_weights
+    derives both from the planes): resN_se_compress holds SE_PER_UNIT entries per unit, half +1 and
+    half -1; resN_se_gating at most one entry +-K per channel (K a power of two), none on about a
+    quarter of them and none from a muted unit, so that every gate is sigmoid(+-K hid) or
+    sigmoid(0): 0, 1/2 or 1 exactly once K hid is large (module docstring).
+
+    leaky_relu, and se_units > 0 without `se`, are refused (module docstring)."""
     assert not desc.leaky_relu, "0.03 is not dyadic"
-    assert not desc.se_units, "the squeeze-excite gate is a sigmoid"
+    assert not desc.se_units or se is not None, "the squeeze-excite gate is a sigmoid: only with saturating gates (se=...)"
+    if se is not None:
+        assert desc.se_units and desc.resnet_v2 and sig_bits(float(se["K"])) == 1, se
     wide = dict(wide or {})
     kind, W = wide.get("kind"), int(wide.get("bits", 0))
     assert kind in (None,) + WIDE_KINDS, kind
@@ -182,6 +249,9 @@ def lattice_weights(desc, seed, *, nnz, wmax, wide=None):
             d = rng.integers(0, 2 ** (W - 2) - 2 ** (W - 5), size=n) * 2 + (1 if odd else rng.integers(0, 2, size=n))
         return top + d
     stream_base, last_conv = None, None
+    # SE on boards whose position count is a power of two: per block (c1, c2, unit), conv2's output
+    # channel c2 a copy of c1 and one compress unit reading +c1 - c2 alone (_se_compress)
+    twins = {}
     # what the BN named by a prefix does: "plain", "w0" (initial_weights), "beta" (stream's initial BN),
     # ("shrink", offset) (a BN behind a conv that reads the wide stream)
     special, single = {}, set()
@@ -214,6 +284,10 @@ def lattice_weights(desc, seed, *, nnz, wmax, wide=None):
                 # stream each: a slip in any trunk channel then reaches a logit)
                 dense_head = head and kind != "policy_dense"
                 k = _sparse(rng, shape, shape[2] // 2 if dense_head else (2 * nnz if head else nnz), wmax, True)
+            if se is not None and name.startswith("res") and name.endswith("_conv2") and sig_bits(float(desc.hw)) == 1:
+                c1, c2 = rng.choice(n, size=2, replace=False)
+                k[..., c2] = k[..., c1]
+                twins[int(name[3:name.index("_")])] = (int(c1), int(c2), int(rng.integers(0, desc.se_units - 1)))
             a = last_conv = k
         elif name.endswith("_gamma"):
             if sp == "w0":
@@ -242,6 +316,11 @@ def lattice_weights(desc, seed, *, nnz, wmax, wide=None):
                 a = np.zeros(n)
             else:
                 a = rng.integers(-1, 2, size=n)
+        elif name.endswith("_se_compress"):
+            a = _se_compress(rng, shape, twins.get(int(name[3:name.index("_")])))
+        elif name.endswith("_se_gating"):
+            blk = int(name[3:name.index("_")])
+            a = _se_gating(rng, shape, float(se["K"]), {j for b, j in se.get("mute", ()) if b == blk}, twins.get(blk))
         elif len(shape) == 2:
             if kind == "policy_dense" and name.startswith("policy"):
                 a = _sparse_dense(rng, shape, 2, 2 ** (W - 2), 2 ** (W - 1) - 1) * 2
@@ -288,9 +367,21 @@ def oracle_weights(weights):
     return out
 
 
-def lattice_planes(desc, n, seed, board_scale=None):
-    """random_planes' 0 / 1 boards; board_scale: one power of two per board."""
+SE_DENSITIES = (1.0, 0.5, 0.25, 0.125)
+
+
+def lattice_planes(desc, n, seed, board_scale=None, mixed_fill=False):
+    """random_planes' 0 / 1 boards; board_scale: one power of two per board; mixed_fill: every set
+    bit is kept with a probability of its (board, input plane), one of SE_DENSITIES at random (board 0:
+    all kept).  Still 0 / 1 planes, but boards whose planes are filled differently have channel means
+    of different proportions, so their squeeze-excite gates differ (random_planes' boards all look
+    alike to a mean)."""
     x = random_planes(desc, n, seed)
+    if mixed_fill:
+        rng = np.random.default_rng([seed, 77])
+        p = rng.choice(SE_DENSITIES, size=(n, desc.input_channels))
+        p[0] = 1.0
+        x = (x * (rng.random(x.shape) < p[:, :, None, None])).astype(np.float32)
     if board_scale is not None:
         s = np.asarray(board_scale, dtype=np.float64)
         assert s.shape == (n,) and np.all(s > 0) and sig_bits(s) == 1, s
@@ -333,17 +424,70 @@ def _conv(x, k, wrap=False):
     return out
 
 
-def _forward(desc, weights, planes, tap=None, hooks=None):
+# A float32 gate 1.f / (1.f + exp(-z)) is exact at three points.  It is 1 once exp(-z) <= 2^-25
+# (1 + 2^-25 ties to even at 1): z >= 25 ln 2 = 17.4.  It is 0 once exp(-z) overflows to +inf (expf,
+# and __expf's v_exp_f32(-z log2 e) alike: past 2^128): z <= -128 ln 2 = -88.8.  It is 1/2 at z = 0
+# (exp(0) = 1).  ZSAT = 128 clears both thresholds with room to spare; the nets are built with every
+# nonzero |z| >= 2 ZSAT, so that a hidden unit with a relative error of up to a half (boards whose
+# position count is no power of two, check_representable) still saturates.
+ZSAT = 128.0
+SE_FAULTS = ("gate_board_swap", "gate_channel_shift_4", "gate_channel_shift_16", "gate_block_slip", "drop_last_unit",
+             "no_relu", "gate_after_add", "mean_one_count")
+
+
+def _se_gates(u, w1, w2, blk, strict, fault=None):
+    """The squeeze-excite gates of conv2's output u [N, H, W, F] as classes, not as a float64 sigmoid:
+    1 where z >= ZSAT, 0 where z <= -ZSAT, 1/2 where every product hid_j w2[j, c] is exactly zero;
+    strict: anything else is an assertion failure (otherwise, for the generator's first walk with
+    K = 1 and for faulty walks: by the sign of z).  The hidden units come from the exact channel sums
+    (sums @ w1 is exact in float64 on these nets; the division by npos keeps sign and zero), so that
+    a pre-activation that cancels to 0 is 0 here whatever the position count.
+    Returns (gate [N, F], info)."""
+    N, H, W, F = u.shape
+    npos = H * W
+    sums = u.sum(axis=(1, 2))
+    if fault and fault[0] == "mean_one_count" and fault[1] == blk:    # one position left out of one channel's sum
+        _, _, b, j = fault
+        pre_j = float(sums[b] @ w1[:, j])
+        delta = -(u[b].reshape(npos, F) * w1[:, j][None, :])          # what leaving (pos, c) out adds to pre_j
+        pos, c = np.unravel_index(np.argmin(delta) if pre_j > 0 else np.argmax(delta), delta.shape)
+        sums = sums.copy()
+        sums[b, c] -= u[b].reshape(npos, F)[pos, c]
+    pre = (sums @ w1) / npos
+    hid = pre if (fault and fault[0] == "no_relu") else np.maximum(pre, 0.0)
+    if fault and fault[0] == "drop_last_unit":
+        hid = hid.copy()
+        hid[:, -1] = 0.0
+    prod = hid[:, :, None] * w2[None, :, :]
+    z = prod.sum(axis=1)
+    half = (prod == 0).all(axis=1)
+    one, zero = (z >= ZSAT, z <= -ZSAT) if strict else (z > 0, z < 0)
+    assert (half | one | zero).all(), ("block %d: %d unsaturated gates, smallest nonzero |z| %g" %
+                                       (blk, int((~(half | one | zero)).sum()), np.abs(z[~half]).min()))
+    gate = np.where(half, 0.5, np.where(one, 1.0, 0.0))
+    if fault and fault[0] == "gate_board_swap":
+        for b in range(0, N - 1, 2):
+            gate[[b, b + 1]] = gate[[b + 1, b]]
+    if fault and fault[0].startswith("gate_channel_shift"):
+        gate = np.roll(gate, int(fault[0].rsplit("_", 1)[1]), axis=1)
+    return gate, dict(sums=sums, pre=pre, hid=hid, prod=prod, z=z, gate=gate, npos=npos)
+
+
+def _forward(desc, weights, planes, tap=None, hooks=None, se_fault=None, se_strict=True):
     """nn_ref.forward(..., logits=True) restated with nn_ref's pieces (_conv_same, _bn, _act).
 
     hooks: {conv name: f(inp, k) -> (inp, k, wrap)} alters one conv's operands (faulty_logits).
     tap(kind, name, inp, k, bn, skip): called for every conv ("trunk" / "head"), every v2
-    pre-activation ("affine": k is None), every Dense ("dense" / "gemm": bn is the bias array) and
-    the pooled mean ("pool").  Returns (logits [policy.., value] float64, final trunk activations)."""
+    pre-activation ("affine": k is None), every Dense ("dense" / "gemm": bn is the bias array), the
+    pooled mean ("pool") and every squeeze-excite ("se": inp is conv2's output, k the (compress,
+    gating) pair, bn _se_gates' info, skip the stream).  se_fault: a tuple whose first item is one
+    of SE_FAULTS (faulty_se_logits).  Squeeze-excite gates are classes (_se_gates), so the walk of
+    an SE net stays on the lattice.
+    Returns (logits [policy.., value] float64, final trunk activations)."""
     w = dict(oracle_weights(weights))
     hooks = hooks or {}
     tap = tap or (lambda *a: None)
-    assert not desc.leaky_relu and not desc.se_units
+    assert not desc.leaky_relu
     act = lambda t: nn_ref._act(t, False)
 
     def conv(x, name, bn, kind, skip=None):
@@ -374,7 +518,16 @@ def _forward(desc, weights, planes, tap=None, hooks=None):
         if v2:
             tap("affine", "res%d_bn1" % i, x, None, "res%d_bn1" % i, None)
             y = act(conv(act(nn_ref._bn(x, w, "res%d_bn1" % i)), "res%d_conv1" % i, "res%d_bn2" % i, "trunk"))
-            x = t + conv(y, "res%d_conv2" % i, None, "trunk", skip=t)
+            if desc.se_units:
+                u = conv(y, "res%d_conv2" % i, None, "trunk")
+                j = 0 if (se_fault and se_fault[0] == "gate_block_slip" and i == 1) else i
+                w1, w2 = (w["res%d_se_%s" % (j, s)].astype(np.float64) for s in ("compress", "gating"))
+                gate, info = _se_gates(u, w1, w2, i, se_strict and not se_fault and not hooks, se_fault)
+                tap("se", "res%d_se" % i, u, (w1, w2), info, t)
+                g = gate[:, None, None, :]
+                x = (t + u) * g if (se_fault and se_fault[0] == "gate_after_add") else t + u * g
+            else:
+                x = t + conv(y, "res%d_conv2" % i, None, "trunk", skip=t)
         else:
             y = act(conv(x, "res%d_conv0" % i, "res%d_bn0" % i, "trunk"))
             x = act(t + conv(y, "res%d_conv1" % i, "res%d_bn1" % i, "trunk", skip=t))
@@ -419,6 +572,8 @@ def lattice_exponent(desc, weights, planes):
             sc, bi = _fold64(w, None, "res%d_bn1" % i)
             y = conv(_emin(_eadd(e, lsb_exp(sc)), lsb_exp(bi)), "res%d_conv1" % i, "res%d_bn2" % i)
             y = conv(y, "res%d_conv2" % i, None)
+            if desc.se_units:      # a gate of 1/2 lowers the lowest set bit by one
+                y = _eadd(y, -1)
         else:
             y = conv(conv(e, "res%d_conv0" % i, "res%d_bn0" % i), "res%d_conv1" % i, "res%d_bn1" % i)
         e = _emin(e, y)
@@ -447,15 +602,26 @@ def expected_logits(desc, weights, planes):
     """oracle/nn_ref.forward(oracle_weights(weights), logits=True) snapped to the lattice unit
     2^lattice_exponent; the snap must move nothing by more than 1e-5 units.  Also asserts that the
     oracle on the float32 vars as they are is the same net: within the drift of its var + 1e-3 over
-    the deepest chain of BNs, relative to the largest logit.  [policy_0, .., value] float64."""
+    the deepest chain of BNs, relative to the largest logit.  [policy_0, .., value] float64.
+
+    Squeeze-excite nets: the expected logits are the walk's (_forward: gates as classes, which
+    asserts that every gate is saturated), which must lie on the lattice as they are; nn_ref.forward,
+    whose float64 sigmoid makes a "0" gate about 1e-100 and whose channel means round where the
+    position count is no power of two, must agree with them within the same 1e-5 units."""
     unit = 2.0 ** lattice_exponent(desc, weights, planes)
-    plain = nn_ref.forward(desc, weights, planes, logits=True)
+    with np.errstate(over="ignore"):      # (a saturated "0" gate: exp(K hid) is inf in float64 too)
+        plain = nn_ref.forward(desc, weights, planes, logits=True)
+        exact = nn_ref.forward(desc, oracle_weights(weights), planes, logits=True)
     depth = 2 * desc.residual_layers + 2
+    walk = _forward(desc, weights, planes)[0] if desc.se_units else None
     out = []
-    for z, zp in zip(nn_ref.forward(desc, oracle_weights(weights), planes, logits=True), plain):
+    for i, (z, zp) in enumerate(zip(exact, plain)):
         q = np.rint(z / unit)
         moved = float(np.abs(z / unit - q).max())
         assert moved <= 1e-5, ("the oracle is %.3g units of %g off the lattice" % (moved, unit))
+        if walk is not None:
+            assert np.array_equal(np.rint(walk[i] / unit) * unit, walk[i]), "the walk of an SE net left the lattice"
+            assert np.array_equal(q * unit, walk[i]), ("nn_ref.forward and the walk disagree", float(np.abs(z - walk[i]).max() / unit))
         out.append(q * unit)
         assert np.abs(zp - z).max() <= 8 * depth * ORACLE_VAR_DRIFT * np.abs(z).max(), (np.abs(zp - z).max(), np.abs(z).max())
     return out
@@ -485,7 +651,15 @@ def check_representable(desc, weights, planes, mode):
       board the largest and the smallest nonzero |input| of a conv less than 2^20 apart, so that
       with the board's exponent (layered_forward.h board_exponent: the largest lies in [2^14, 2^15))
       hi parts and the scaled lo parts stay clear of fp16's subnormals;
-    * a pooling value head only where the position count is a power of two.
+    * a pooling value head only where the position count is a power of two;
+    * squeeze-excite: every gate is a class (the walk refuses an unsaturated one) and every nonzero
+      |z| >= 2 ZSAT; the gating matrix has at most one power of two per channel, some channel reads
+      the last unit (and, S > 64, a unit >= 64); every channel sum fits 24 bits of its board's
+      lattice; the gated add s + u g, with u / 2 counted on its own lower lattice, stays below 2^24
+      units.  Position count a power of two: the means, both Denses' sums of |terms| and hid K fit
+      24 bits too, so the gate path is exact in any order, and some hidden unit that a gate reads
+      lies within one lattice step of 0 (returned: [(name, board, unit)]).  Otherwise: no unit that
+      a gate reads is within twice the float32 error bound of 0 (se_fragile_units).
     """
     bits, hi = MODE_BITS[mode], HI_BITS.get(mode)
     w = dict(weights)
@@ -509,7 +683,44 @@ def check_representable(desc, weights, planes, mode):
         if part is not None:
             assert bw <= part or bx <= part, (mode, name, "lo x lo is dropped: weights %d bits, inputs %d, hi part %d" % (bw, bx, part))
 
+    near_zero = []      # SE, power-of-two boards: (name, board, unit) of fed units within a lattice step of 0
+
+    def se(name, u, w1, w2, info, t):
+        npos, sums, hid, prod, z, gate = (info[s] for s in ("npos", "sums", "hid", "prod", "z", "gate"))
+        assert np.isin(gate, (0.0, 0.5, 1.0)).all()
+        assert ((w2 != 0).sum(axis=0) <= 1).all() and sig_bits(w2) <= 1, (name, "gating: one power of two per channel at most")
+        fed = (w2 != 0).any(axis=1)
+        assert np.abs(z[(prod != 0).any(axis=1)]).min() >= 2 * ZSAT, (name, "a nonzero z below 2 ZSAT")
+        pow2 = sig_bits(float(npos)) == 1
+        eu = [lsb_exp(u[b]) for b in range(u.shape[0])]
+        for b, e in enumerate(eu):
+            if e is None:
+                continue
+            # the channel sums are exact in any order, on every board
+            assert np.abs(u[b]).sum(axis=(0, 1)).max() < 2.0 ** (ACC_BITS + e), (mode, name, b, "channel sums")
+            mean = sums[b] / npos
+            terms = np.abs(w1 * mean[:, None])                    # [F, S]
+            if pow2:
+                # means, both Denses' partial sums and hid K: 24 bits in any summation order
+                em = e - int(np.log2(npos))
+                assert np.array_equal(np.ldexp(sums[b], -int(np.log2(npos))), mean)
+                assert terms.sum(axis=0).max() < 2.0 ** (ACC_BITS + em + lsb_exp(w1)), (mode, name, b, "compress sums")
+                eh = lsb_exp(hid[b])
+                if eh is not None:
+                    assert np.abs(prod[b]).sum(axis=0).max() < 2.0 ** (ACC_BITS + eh + lsb_exp(w2)), (mode, name, b, "gating sums")
+                    assert sig_bits(prod[b]) <= ACC_BITS
+                near_zero.extend((name, b, int(j)) for j in np.nonzero(fed & (np.abs(sums[b] @ w1) <= 2.0 ** e))[0])
+            else:
+                bad = se_fragile_units(sums[b], w1, npos) & fed
+                assert not bad.any(), (mode, name, b, "hidden units %s are within the float32 error of 0" % np.nonzero(bad)[0])
+            ug = u[b] * gate[b][None, None, :]
+            ea = _emin(lsb_exp(t[b]), lsb_exp(ug))
+            if ea is not None:
+                assert (np.abs(t[b]) + np.abs(ug)).max() < 2.0 ** (ACC_BITS + ea), (mode, name, b, "the gated add")
+
     def tap(kind, name, inp, k, bn, skip):
+        if kind == "se":
+            return se(name, inp, k[0], k[1], bn, skip)
         if kind == "pool":
             assert sig_bits(float(desc.hw)) == 1, (name, "1 / %d is not a power of two" % desc.hw)
             s = np.abs(inp).sum(axis=(1, 2))
@@ -546,6 +757,108 @@ def check_representable(desc, weights, planes, mode):
         sums(name, inp, kf, bi, skip, True)
 
     _forward(desc, weights, planes, tap=tap)
+    if desc.se_units:
+        S = desc.se_units
+        for i in range(desc.residual_layers):
+            reads = np.nonzero(w["res%d_se_gating" % i])[0]
+            assert S - 1 in reads and (S <= 64 or (reads >= 64).any()), (i, "some channel must read the last unit, and a unit >= 64")
+        if sig_bits(float(desc.hw)) == 1:
+            assert near_zero, "no fed hidden unit sits at 0 or within one lattice step of it: a mean off by one count would not show"
+    return near_zero
+
+
+def se_fragile_units(sums, w1, npos):
+    """Boards whose position count is no power of two: the mean is sum * fl32(1 / npos), so the
+    hidden units carry a rounding error.  [S] bool: the units of one board (channel sums [F]) whose
+    pre-activation does not exceed twice the float32 error bound
+        (F + 2) 2^-24 sum_c |w1[c, j] mean_c|
+    (fl32(1 / npos) and the product by it: 2 roundings; each product w1 mean: exact for +-1, at most 1;
+    F - 1 additions, serial or in four partial sums; first order, hence "twice") although some term
+    is nonzero: such a unit could come out with the wrong sign, or as +-tiny where the oracle has 0,
+    and tiny * K is an unsaturated gate.  It must feed no channel."""
+    F = w1.shape[0]
+    mean = sums / npos
+    mag = np.abs(w1 * mean[:, None]).sum(axis=0)
+    pre = np.abs(sums @ w1) / npos
+    return (mag > 0) & (pre <= 2.0 * (F + 2) * 2.0 ** -24 * mag)
+
+
+def se_walk(desc, weights, planes, strict=True):
+    """[(name, u, w1, w2, info)] per squeeze-excite block of the (clean) walk."""
+    seen = []
+
+    def tap(kind, name, inp, k, bn, skip):
+        if kind == "se":
+            seen.append((name, inp, k[0], k[1], bn))
+    _forward(desc, weights, planes, tap=tap, se_strict=strict)
+    return seen
+
+
+def lattice_se_weights(desc, seed, planes, *, nnz, wmax, homogeneous=False):
+    """lattice_weights for a squeeze-excite net on these planes, K and the muted units derived, not
+    tuned: walks the net with K = 1 and gates by the sign of z; on boards whose position count is no
+    power of two, mutes (zeroes the gating row of) every fed unit that se_fragile_units names on any
+    board, until none is left; K is then the smallest power of two for which every nonzero oracle
+    z has |z| >= 2 ZSAT = 256.  (Gates by sign are the saturated gates, so K changes no gate.)
+    homogeneous: with zero_trunk_shifts, as the walks see them."""
+    def make(K):
+        w = lattice_weights(desc, seed, nnz=nnz, wmax=wmax, se={"K": K, "mute": mute})
+        return zero_trunk_shifts(desc, w) if homogeneous else w
+    mute = set()
+    pow2 = sig_bits(float(desc.hw)) == 1
+    for _ in range(8):
+        w = make(1.0)
+        walk = se_walk(desc, w, planes, strict=False)
+        new = set()
+        if not pow2:
+            for i, (_, u, w1, w2, info) in enumerate(walk):
+                fed = (w2 != 0).any(axis=1)
+                for b in range(u.shape[0]):
+                    new |= {(i, int(j)) for j in np.nonzero(se_fragile_units(info["sums"][b], w1, info["npos"]) & fed)[0]}
+        if not new:
+            break
+        mute |= new
+    else:
+        raise AssertionError("muting fragile units did not settle")
+    zmin = min(np.abs(info["z"][(info["prod"] != 0).any(axis=1)]).min() for _, _, _, _, info in walk)
+    K = 2.0 ** int(np.ceil(np.log2(2 * ZSAT / zmin)))
+    return make(K)
+
+
+def se_liveness(desc, weights, planes):
+    """Per squeeze-excite block, on the oracle alone: (the shares of the (board, channel) pairs whose
+    gate is 0, 1/2 and 1, the smallest number of channels in which two boards' gates differ)."""
+    out = []
+    for _, _, _, _, info in se_walk(desc, weights, planes):
+        g = info["gate"]
+        diff = min([int((g[a] != g[b]).sum()) for a in range(len(g)) for b in range(a)] or [g.shape[1]])
+        out.append(([float((g == v).mean()) for v in (0.0, 0.5, 1.0)], diff))
+    return out
+
+
+def faulty_se_logits(desc, weights, planes, fault):
+    """The logits of a forward whose squeeze-excite slips the way a wrong kernel would (oracle side
+    only): boards 2k and 2k + 1 exchange gate vectors; the gate vector rotated by a lane group (4) or a
+    co tile (16); block 1 with block 0's compress and gating matrices; the last hidden unit dropped;
+    negative hidden values passed; (s + u) g for s + u g; one position's value left out of one
+    channel's sum (in the block and board whose fed hidden unit is nearest 0, at the position and
+    channel that move it furthest towards or across 0)."""
+    assert fault in SE_FAULTS, fault
+    f = (fault,)
+    if fault == "mean_one_count":
+        best = None
+        for i, (_, u, w1, w2, info) in enumerate(se_walk(desc, weights, planes)):
+            fed = np.nonzero((w2 != 0).any(axis=1))[0]
+            for b in range(u.shape[0]):
+                e = lsb_exp(u[b])
+                if e is None:
+                    continue
+                d = np.abs(info["sums"][b] @ w1[:, fed]) / 2.0 ** e
+                j = int(np.argmin(d))
+                if best is None or d[j] < best[0]:
+                    best = (float(d[j]), i, b, int(fed[j]))
+        f = (fault,) + best[1:]
+    return _forward(desc, weights, planes, se_fault=f)[0]
 
 
 # ---- faults, on the oracle side only ------------------------------------------------------------------

@@ -1,17 +1,34 @@
 """CPU side of the exact suite (tests/test_nn_exact_gpu.py): every net of that file meets, for every
 mode it is run in, the conditions under which exactness is a theorem (exact_lattice.
 check_representable); the nets are alive; and the comparison would notice a wrong kernel -- each
-kernel-like slip, applied to the oracle side alone, moves at least one expected logit.  No GPU."""
+kernel-like slip, applied to the oracle side alone, moves at least one expected logit.  For the
+squeeze-excite nets that includes the saturation conditions (every gate exactly 0, 1/2 or 1), gates
+that take all three values and differ between the boards of a launch, and the slips a squeeze-excite
+kernel can make (exact_lattice.SE_FAULTS).  No GPU."""
+import dataclasses
+
 import numpy as np
 import pytest
 
 import exact_lattice as xl
 from galvanise_zero_amd.nn.desc import NetDesc
 from oracle import nn_ref
-from test_nn_exact_gpu import ALL, CASES, CHUNKED, LARGE_ROWS, PROBABILITY, SCALES, build
+from test_nn_exact_gpu import ALL, CASES, CHUNKED, LARGE_ROWS, PROBABILITY, SCALES, SE_CASES, SE_VARIED, build
 
 FAMILIES = {c.family: name for name, c in CASES.items() if c.family}
 GEOMETRY_FAULTS = ("tap_swap", "wrap_pad", "channel_swap", "drop_last_channel")
+SE_FAMILIES = {c.family: name for name, c in SE_CASES.items()}
+
+
+def _pow2_board(desc):
+    return xl.sig_bits(float(desc.hw)) == 1
+
+
+def _se_fault_applies(name, fault):
+    """gate_block_slip needs a block 1; mean_one_count is for the boards on which the mean is exact
+    (elsewhere a saturated gate cannot see a small error of the mean, by construction)."""
+    desc = SE_CASES[name].desc
+    return not (fault == "gate_block_slip" and desc.residual_layers < 2) and not (fault == "mean_one_count" and not _pow2_board(desc))
 
 
 def _last_residual_conv(desc):
@@ -36,6 +53,12 @@ def test_generator_refuses_inexact_flags():
     for flag in (dict(leaky_relu=True), dict(resnet_v2=True, se_units=42)):
         with pytest.raises(AssertionError):
             xl.lattice_weights(NetDesc(5, 8, 8, 128, 1, [155, 155], **flag), 1, nnz=2, wmax=1)
+    # a squeeze-excite net that violates a condition: a gating entry of 2^4 is an unsaturated gate
+    desc, w, x, _ = build(SE_VARIED)
+    xl.check_representable(desc, w, x, "fp32-ieee")
+    bad = [(n, (np.sign(a) * 16.0).astype(np.float32) if n == "res1_se_gating" else a) for n, a in w]
+    with pytest.raises(AssertionError, match="unsaturated"):
+        xl.check_representable(desc, bad, x, "fp32-ieee")
 
 
 def test_generator_covers_the_lattice():
@@ -56,12 +79,20 @@ def test_generator_covers_the_lattice():
 
 
 @pytest.mark.parametrize("name", ["8x8_f128_b2", "v2_8x8_f128_b2_pool", "v2_13x13_f256_b2_concat", "6x9_legacy_f40_b2",
-                                  "v2_10x10_f256_b1_bare"])
+                                  "v2_10x10_f256_b1_bare"] + sorted(SE_CASES))
 def test_walk_is_the_oracle(name):
-    """exact_lattice._forward, which the conditions and the faults walk, is nn_ref.forward."""
+    """exact_lattice._forward, which the conditions and the faults walk, is nn_ref.forward.  On a
+    squeeze-excite net the walk's gates are the classes 0, 1/2, 1 and nn_ref's a float64 sigmoid (a
+    "0" gate is about 1e-100 there), so the two are compared after the snap to the lattice."""
     desc, w, x, expected = build(name)
     ours, _ = xl._forward(desc, w, x)
-    for a, b, e in zip(ours, nn_ref.forward(desc, xl.oracle_weights(w), x, logits=True), expected):
+    with np.errstate(over="ignore"):
+        ref = nn_ref.forward(desc, xl.oracle_weights(w), x, logits=True)
+    unit = 2.0 ** xl.lattice_exponent(desc, w, x)
+    for a, b, e in zip(ours, ref, expected):
+        if desc.se_units:
+            assert np.abs(b / unit - np.rint(b / unit)).max() <= 1e-5
+            b = np.rint(b / unit) * unit
         assert np.array_equal(a, b) and np.array_equal(a, e)
 
 
@@ -79,12 +110,48 @@ def test_conditions(name):
                 xl.check_representable(desc, w, x, mode)
 
 
-@pytest.mark.parametrize("rows,names", [(5, ("8x8_f128_b2", CHUNKED)), (LARGE_ROWS, ("8x8_f128_b2",))])
+@pytest.mark.parametrize("rows,names", [(5, ("8x8_f128_b2", CHUNKED, SE_VARIED)), (LARGE_ROWS, ("8x8_f128_b2",))])
 def test_conditions_at_other_row_counts(rows, names):
     for name in names:
         desc, w, x, _ = build(name, rows)
         for mode in CASES[name].modes:
             xl.check_representable(desc, w, x, mode)
+
+
+@pytest.mark.parametrize("name,rows", [(name, None) for name in sorted(SE_CASES)] + [(SE_VARIED, 5)])
+def test_se_lattice(name, rows):
+    """The squeeze-excite nets are what the generator says: balanced +-1 compress units, at most one
+    +-K per gating column with about a quarter of the columns empty, the last unit read, K derived
+    (the smallest power of two with every nonzero oracle |z| >= 256, so the smallest lies in
+    [256, 512)), every gate one of 0, 1/2, 1, and the lattice unit one step lower per block; on the
+    boards whose position count is a power of two some fed hidden unit sits within a lattice step
+    of 0 (check_representable returns them), on the others every fed unit clears the float32 error
+    bound of its sum (se_fragile_units)."""
+    desc, w, x, _ = build(name, rows)
+    wd = dict(w)
+    S, F = desc.se_units, desc.cnn_filter_size
+    zmin = np.inf
+    for i, (_, u, w1, w2, info) in enumerate(xl.se_walk(desc, w, x)):
+        assert np.array_equal(w1, wd["res%d_se_compress" % i]) and np.array_equal(w2, wd["res%d_se_gating" % i])
+        assert w1.shape == (F, S) and set(np.unique(w1)) == {-1.0, 0.0, 1.0} and np.all(w1.sum(axis=0) == 0)
+        per_column = (w2 != 0).sum(axis=0)
+        assert per_column.max() == 1 and 0.1 <= (per_column == 0).mean() <= 0.4
+        K = np.abs(w2).max()
+        assert set(np.unique(np.abs(w2))) == {0.0, K} and xl.sig_bits(K) == 1
+        assert (w2[S - 1] != 0).any() and (S <= 64 or (w2[64:] != 0).any())
+        assert np.isin(info["gate"], (0.0, 0.5, 1.0)).all()
+        zmin = min(zmin, np.abs(info["z"][(info["prod"] != 0).any(axis=1)]).min())
+        if not _pow2_board(desc):
+            fed = (w2 != 0).any(axis=1)
+            for b in range(x.shape[0]):
+                assert not (xl.se_fragile_units(info["sums"][b], w1, info["npos"]) & fed).any()
+    assert 256 <= zmin < 512
+    near = xl.check_representable(desc, w, x, CASES[name].modes[0])
+    assert bool(near) == _pow2_board(desc)
+    plain = [(n, a) for n, a in w if "_se_" not in n]
+    lowered = xl.lattice_exponent(dataclasses.replace(desc, se_units=0), plain, x) - xl.lattice_exponent(desc, w, x)
+    # (one step per block on the path to the logits; the concat head also reads the earlier layers)
+    assert 1 <= lowered <= desc.residual_layers and (lowered == desc.residual_layers or desc.concat_all_layers)
 
 
 def test_wide_cases_use_the_width():
@@ -119,6 +186,42 @@ def test_liveness(name):
     for z in expected[:-1]:
         assert len(np.unique(z)) >= 32
     assert len(np.unique(expected[-1])) > 1
+    if name in SE_CASES:
+        _se_liveness(desc, w, x)
+
+
+def _se_liveness(desc, w, x):
+    """In every block all three gate values occur, each on at least 10 % of the (board, channel)
+    pairs, and every pair of boards in the launch differs in at least 4 channels' gates."""
+    live = xl.se_liveness(desc, w, x)
+    assert len(live) == desc.residual_layers
+    for shares, differ in live:
+        assert min(shares) >= 0.10 and abs(sum(shares) - 1.0) < 1e-12, shares
+        assert differ >= 4, differ
+
+
+def test_se_liveness_at_5_rows():
+    desc, w, x, _ = build(SE_VARIED, 5)
+    assert x.shape[0] == 5
+    _se_liveness(desc, w, x)
+
+
+@pytest.mark.parametrize("family,fault", [(f, fault) for f in sorted(SE_FAMILIES) for fault in xl.SE_FAULTS
+                                          if _se_fault_applies(SE_FAMILIES[f], fault)])
+def test_se_fault_is_seen(family, fault):
+    """Each slip a squeeze-excite kernel can make, on the oracle side alone, moves a logit: a
+    neighbouring board's gates, gates off by a lane group or a co tile, another block's matrices, the
+    last unit dropped, no relu, the gate applied after the add, a mean one count short."""
+    desc, w, x, expected = build(SE_FAMILIES[family])
+    assert _differs(xl.faulty_se_logits(desc, w, x, fault), expected)
+
+
+def test_se_faults_cover_every_family():
+    """Every fault is shown on every SE family where it can occur (_se_fault_applies)."""
+    for fault in xl.SE_FAULTS:
+        on = [f for f, name in SE_FAMILIES.items() if _se_fault_applies(name, fault)]
+        assert len(on) >= (4 if fault == "mean_one_count" else 6), (fault, on)
+    assert len(SE_FAMILIES) == len(SE_CASES) == 8
 
 
 @pytest.mark.parametrize("fault", GEOMETRY_FAULTS)
@@ -194,4 +297,4 @@ def test_every_mode_and_family_is_run():
     for mode in ALL:
         assert '"%s"' % mode in section or "`\"%s\"`" % mode in section, mode
     assert {m for _, m in PROBABILITY} == set(ALL)
-    assert len(FAMILIES) >= 9
+    assert len(FAMILIES) >= 9 + len(SE_FAMILIES) and len(SE_FAMILIES) == 8

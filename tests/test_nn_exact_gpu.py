@@ -9,10 +9,14 @@ measured on the kernels; the one bounded comparison, test_probabilities, isolate
 on exact logits and asserts the project's DAMPED_TOLERANCE.
 
 A net is listed with the modes whose conditions it meets and whose kernels take it; nets that need
-more bits than a mode has are not run in that mode.  Left to the tolerance tests: leaky and
-squeeze-excite nets, and the pooling value head on boards whose position count is no power of two
+more bits than a mode has are not run in that mode.  Squeeze-excite nets are in (SE_CASES), on
+weights and planes that saturate every gate at exactly 0, 1/2 or 1 (exact_lattice's docstring): the
+two-image and the single-image / two-pass gate paths of the fused kernels and the layered modes'
+gate and apply kernels, under each kernel variant and across row chunks.  Left to the tolerance
+tests: leaky nets, the pooling value head on boards whose position count is no power of two
 (exact_lattice's docstring: the channel mean multiplies by fl32(1 / npos), forward_kernel.h
-"sm[r] * inv").
+"sm[r] * inv"), and small errors in the scale of the squeeze-excite mean on such boards, which a
+saturated gate cannot see by construction.
 """
 import dataclasses
 
@@ -36,6 +40,7 @@ LEGACY = dict(flatten_nchw=True, conv_bias=True, value_bn=True, value_sigmoid=Tr
 F128 = NetDesc(5, 8, 8, 128, 2, [155, 155])
 WIDE_NET = NetDesc(5, 8, 8, 128, 1, [155, 155], value_bn=True)
 GEMM_NET = NetDesc(12, 10, 10, 256, 1, [3041, 3041], value_bn=True)
+V2_POOL = dict(resnet_v2=True, global_pooling_value=True, value_bn=True)
 
 
 @dataclasses.dataclass
@@ -51,6 +56,8 @@ class Case:
     homogeneous: bool = False     # trunk shifts zeroed (exact_lattice.zero_trunk_shifts)
     exhaustive: bool = False      # modes = every mode whose conditions hold (test_nn_exact.py asserts it)
     family: str = None            # kernel family this net represents in test_nn_exact.py's fault checks
+    se: bool = False              # squeeze-excite with saturated gates (exact_lattice.lattice_se_weights)
+    plane_seed: int = None        # SE nets: the planes' seed (default 100 + rows), chosen for the liveness conditions
 
 
 CASES = {
@@ -87,11 +94,44 @@ CASES = {
     "8x8_scaled": Case(F128, ALL, scales=SCALES, homogeneous=True, exhaustive=True, seed=4),
     "8x8_scaled_permuted": Case(F128, ALL, scales=SCALES, order=(2, 0, 3, 1), homogeneous=True, exhaustive=True, seed=4),
 }
+SE = dict(se=True, homogeneous=True)
+SE_CASES = {
+    # ---- squeeze-excite with saturated gates (0, 1/2, 1 exactly): se_gates / squeeze_excite in the fused
+    # kernels, se_gate_kernel / se_apply_kernel in the four layered modes.  Trunk shifts zeroed and planes of
+    # mixed fill, so that the channel means' proportions, and with them the gates, differ from board to board;
+    # the seeds are those at which test_nn_exact.py's conditions, liveness and fault checks all hold ----
+    # the two-image squeeze_excite, and the layered kernels
+    "se_8x8_f128_b2_s42_pool": Case(NetDesc(5, 8, 8, 128, 2, [155, 155], se_units=42, **V2_POOL), ALL, family="se_two_image_f128",
+                                    seed=2, plane_seed=200, **SE),
+    "se_8x8_f64_b3_s21": Case(NetDesc(5, 8, 8, 64, 3, [155, 155], se_units=21, **V2_POOL), FUSED, family="se_f64",
+                              seed=8, plane_seed=200, **SE),
+    # se_gate_kernel's j += FP loop runs twice
+    "se_8x8_f64_b1_s128": Case(NetDesc(5, 8, 8, 64, 1, [155, 155], se_units=128, **V2_POOL), LAYERED,
+                               family="se_layered_s128", seed=1, plane_seed=100, **SE),
+    # F padded to 128: the padded channels' means and compress rows must contribute nothing
+    "se_8x8_f80_b2_s26_concat": Case(NetDesc(5, 8, 8, 80, 2, [155, 155], value_hidden_size=128, resnet_v2=True, se_units=26,
+                                             concat_all_layers=True), FUSED + ("fp32-ieee",), family="se_f80_padded",
+                                     seed=1, plane_seed=200, **SE),
+    # the single-image / ADDB path, S no multiple of 4
+    "se_8x8_f256_b2_s85": Case(NetDesc(5, 8, 8, 256, 2, [155, 155], se_units=85, **V2_POOL), FUSED,
+                               family="se_single_image_f256", seed=1, plane_seed=100, **SE),
+    # the two-pass split, a partial last position tile under the 16 * pt + li < npos guard
+    "se_13x13_f256_b2_s85": Case(NetDesc(5, 13, 13, 256, 2, [170, 171], resnet_v2=True, se_units=85), FUSED,
+                                 family="se_two_pass_f256", seed=1, plane_seed=100, **SE),
+    "se_10x10_f192_b2_s64_v3": Case(NetDesc(12, 10, 10, 192, 2, [101, 101], num_values=3, resnet_v2=True, se_units=64), FUSED,
+                                    family="se_f192_padded", seed=2, plane_seed=100, **SE),
+    "se_19x19_f128_b1_s42": Case(NetDesc(5, 19, 19, 128, 1, [362, 362], resnet_v2=True, se_units=42), ALL,
+                                 family="se_19x19", seed=4, plane_seed=200, **SE),
+}
+CASES.update(SE_CASES)
 # one net at 5 rows in 2-row chunks (GZ_FP32_CHUNK_ROWS, read at net creation): the last chunk partial
 CHUNKED = "6x9_legacy_f40_b2"
 # kernel variants (GZ_KERNEL_VARIANT) on the first net at 5 rows: two boards per workgroup, a dead
 # board in the last
 VARIANTS = [("bf16", v) for v in ("11", "12", "21")] + [("bf16x3", v) for v in ("11", "21", "22", "23", "24", "25")]
+# the first SE net at 5 rows under every variant that the v2 kernels of its geometry accept, and in 2-row chunks
+SE_VARIED = "se_8x8_f128_b2_s42_pool"
+SE_VARIANTS = [("bf16", v, 1) for v in ("11", "12", "21")] + [("bf16x3", v, 3) for v in ("11", "21")]
 LARGE_ROWS = 300       # above large_min_rows() = 257: the large-launch default runs
 PROBABILITY = [("8x8_f128_b2", "bf16"), ("8x8_f128_b2", "bf16x3"), ("13x13_f256_b2", "bf16x3"),
                ("10x10_c12_f256_b1_gemm", "bf16x3"), ("v2_8x8_f128_b2_pool", "bf16x3"), ("v2_13x13_f256_b2_concat", "bf16x3"),
@@ -103,15 +143,21 @@ _cache = {}
 
 def build(name, rows=None):
     """(desc, weights, planes, expected logits) of a case, computed once; rows: another row count on the
-    same weights (its planes from their own seed)."""
+    same weights (its planes from their own seed; an SE net's gating scale K is derived from them)."""
     key = (name, rows)
     if key not in _cache:
         c = CASES[name]
-        w = xl.lattice_weights(c.desc, c.seed, nnz=c.nnz, wmax=c.wmax, wide=c.wide)
-        if c.homogeneous:
-            w = xl.zero_trunk_shifts(c.desc, w)
         n = rows or (len(c.scales) if c.scales else max(ROWS))
-        x = xl.lattice_planes(c.desc, n, 100 + n, board_scale=c.scales if not rows else None)
+        if c.se:
+            # every (board, plane) keeps its set bits with a probability of its own: boards filled
+            # differently have different gates (test_nn_exact.py::test_liveness)
+            x = xl.lattice_planes(c.desc, n, (c.plane_seed or 100) + n, mixed_fill=True)
+            w = xl.lattice_se_weights(c.desc, c.seed, x, nnz=c.nnz, wmax=c.wmax, homogeneous=c.homogeneous)
+        else:
+            w = xl.lattice_weights(c.desc, c.seed, nnz=c.nnz, wmax=c.wmax, wide=c.wide)
+            x = xl.lattice_planes(c.desc, n, 100 + n, board_scale=c.scales if not rows else None)
+        if c.homogeneous and not c.se:
+            w = xl.zero_trunk_shifts(c.desc, w)
         if c.order:
             x = np.ascontiguousarray(x[list(c.order)])
         _cache[key] = (c.desc, w, x, xl.expected_logits(c.desc, w, x))
@@ -159,6 +205,20 @@ def test_variants(mode, variant, hip_device, monkeypatch):
     net.close()
 
 
+@pytest.mark.parametrize("mode,variant,parts", SE_VARIANTS)
+def test_se_variants(mode, variant, parts, hip_device, monkeypatch):
+    """The squeeze-excite net at 5 rows and at 2 under each kernel variant (two boards per workgroup:
+    each board its own gates; a dead board in the last workgroup), and the intended kernel ran."""
+    desc, w, x, expected = build(SE_VARIED, 5)
+    monkeypatch.setenv("GZ_KERNEL_VARIANT", variant)
+    net = _net(desc, w, hip_device, mode)
+    kernel = "gznn::trunk_kernel_v2<128, 4, %s, %s, %d>" % (variant[0], variant[1], parts)
+    assert net.kernel_name(False) == net.kernel_name(True) == kernel
+    for n in (5, 2):
+        _assert_exact((mode, variant), net, x, expected, n)
+    net.close()
+
+
 def test_large_launch_default(hip_device, monkeypatch):
     """300 rows with no override: the large-launch default (the in-place split kernel) is what runs."""
     desc, w, x, expected = build("8x8_f128_b2", LARGE_ROWS)
@@ -177,6 +237,16 @@ def test_partial_chunk(mode, hip_device, monkeypatch):
     monkeypatch.setenv("GZ_FP32_CHUNK_ROWS", "2")
     net = _net(desc, w, hip_device, mode)
     _assert_exact((mode, "chunks of 2"), net, x, expected, 5)
+    net.close()
+
+
+@pytest.mark.parametrize("mode", LAYERED)
+def test_se_partial_chunk(mode, hip_device, monkeypatch):
+    """The gate buffer's row indexing across chunks: 5 rows in chunks of 2."""
+    desc, w, x, expected = build(SE_VARIED, 5)
+    monkeypatch.setenv("GZ_FP32_CHUNK_ROWS", "2")
+    net = _net(desc, w, hip_device, mode)
+    _assert_exact((mode, "SE, chunks of 2"), net, x, expected, 5)
     net.close()
 
 
