@@ -104,6 +104,7 @@ def canonical_precision(precision):
 
 
 _FP = ctypes.POINTER(ctypes.c_float)
+_IP = ctypes.POINTER(ctypes.c_int)
 GZ_MAX_SEGMENTS = 32
 
 
@@ -186,8 +187,50 @@ def nn_lib():
             lib.gz_nn_compare_outputs.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                                   ctypes.c_int, ctypes.POINTER(_FP), _FP, ctypes.POINTER(_FP), _FP,
                                                   ctypes.POINTER(GzShadowStats)]
+        if hasattr(lib, "gz_symmetry_create"):   # (absent from older A/B builds loaded through GZ_LIB_DIR)
+            lib.gz_symmetry_create.restype = ctypes.c_void_p
+            lib.gz_symmetry_create.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, _IP, ctypes.c_int, _IP,
+                                               ctypes.POINTER(_IP)]
+            lib.gz_symmetry_destroy.argtypes = [ctypes.c_void_p]
+            lib.gz_symmetry_count.argtypes = [ctypes.c_void_p]
+            lib.gz_net_forward_sym.argtypes = [ctypes.c_void_p, ctypes.c_void_p, _FP, ctypes.c_int, ctypes.POINTER(_FP), _FP]
+            lib.gz_net_forward_sym_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]
         lib._gz_typed = True
     return lib
+
+
+class HipSymmetry(object):
+    """Owner of a gz_symmetry handle (include/gzero_nn.h): the tables of S <= 8 board symmetries for
+    gz_net_forward_sym.  plane_src: int [S][C * H * W]; move_src: per role int [S][P_r] (the fields of
+    util.symmetry.SymmetryTables, or arbitrary permutations).  Creation validates the tables and
+    touches no device; the first forward uploads them."""
+
+    def __init__(self, plane_src, move_src, device=0):
+        self.lib = nn_lib()
+        self.plane_src = np.ascontiguousarray(plane_src, dtype=np.int32)
+        self.move_src = [np.ascontiguousarray(m, dtype=np.int32) for m in move_src]
+        if self.plane_src.ndim != 2 or any(m.ndim != 2 or m.shape[0] != self.plane_src.shape[0] for m in self.move_src):
+            raise ValueError("symmetry tables: plane_src [S][E] and one [S][P_r] move table per role")
+        self.count = self.plane_src.shape[0]
+        self.policy_sizes = [m.shape[1] for m in self.move_src]
+        sizes = (ctypes.c_int * len(self.move_src))(*self.policy_sizes)
+        moves = (_IP * len(self.move_src))(*[m.ctypes.data_as(_IP) for m in self.move_src])
+        self.handle = self.lib.gz_symmetry_create(device, self.count, self.plane_src.shape[1], self.plane_src.ctypes.data_as(_IP),
+                                                  len(self.move_src), sizes, moves)
+        if not self.handle:
+            raise RuntimeError("gz_symmetry_create failed: %s" % self.lib.gz_nn_last_error().decode())
+
+    def close(self):
+        if self.handle:
+            self.lib.gz_symmetry_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def make_net_desc(desc, precision=GZ_PRECISION_BF16):
@@ -271,6 +314,7 @@ class HipNet(object):
         if not self.handle:
             raise RuntimeError("gz_net_create failed: %s" % self.lib.gz_nn_last_error().decode())
         self.weight_count = self.lib.gz_net_weight_count(self.handle)
+        self.device = device
 
     def _check(self, rc, what):
         if rc != 0:
@@ -299,7 +343,15 @@ class HipNet(object):
             raise RuntimeError("gz_net_copy_weight_image failed")
         return buf
 
-    def forward(self, planes):
+    def make_symmetry(self, tables):
+        """A HipSymmetry on this net's device from `tables`: a util.symmetry.SymmetryTables (or any
+        object with plane_src [S][C * H * W] and move_src, one [S][P_r] per role).  Pass it to
+        forward(X, symmetry=...); that the tables fit this net is checked by the forward."""
+        return HipSymmetry(tables.plane_src, tables.move_src, self.device)
+
+    def forward(self, planes, symmetry=None):
+        """symmetry: None, or a HipSymmetry (make_symmetry): the forward averaged over its board
+        symmetries (gz_net_forward_sym, include/gzero_nn.h)."""
         d = self.desc
         planes = np.ascontiguousarray(planes, dtype=np.float32)
         n = planes.shape[0]
@@ -307,6 +359,10 @@ class HipNet(object):
         pols = [np.empty((n, p), dtype=np.float32) for p in d.policy_dist_count]
         val = np.empty((n, d.num_values), dtype=np.float32)
         arr = (_FP * len(pols))(*[_fptr(p) for p in pols])
+        if symmetry is not None:
+            self._check(self.lib.gz_net_forward_sym(self.handle, symmetry.handle, _fptr(planes), n, arr, _fptr(val)),
+                        "gz_net_forward_sym")
+            return pols + [val]
         self._check(self.lib.gz_net_forward(self.handle, _fptr(planes), n, arr, _fptr(val)),
                     "gz_net_forward")
         return pols + [val]
@@ -317,6 +373,14 @@ class HipNet(object):
                                                    ctypes.c_void_p(d_planes), n, arr,
                                                    ctypes.c_void_p(d_values)),
                     "gz_net_forward_device")
+
+    def forward_sym_device(self, symmetry, stream, d_planes, n, d_policies, d_values):
+        """gz_net_forward_sym_device: the symmetry ensemble on `stream`, device pointers as forward_device.
+        One HipSymmetry serves one stream at a time (its scratch)."""
+        arr = (ctypes.c_void_p * len(d_policies))(*d_policies)
+        self._check(self.lib.gz_net_forward_sym_device(self.handle, symmetry.handle, ctypes.c_void_p(stream),
+                                                       ctypes.c_void_p(d_planes), n, arr, ctypes.c_void_p(d_values)),
+                    "gz_net_forward_sym_device")
 
     def forward_segments(self, stream, segments):
         """Asynchronous segmented launch on `stream`: segments = [(rows, planes_ptr, [policy_ptr per
@@ -494,7 +558,6 @@ def verified_decisions():
 
 _VP = ctypes.c_void_p
 _U64P = ctypes.POINTER(ctypes.c_uint64)
-_IP = ctypes.POINTER(ctypes.c_int)
 
 _ENGINE_SIGS = {
     "gz_engine_last_error": (ctypes.c_char_p, []),

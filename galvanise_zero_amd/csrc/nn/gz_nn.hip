@@ -9,6 +9,7 @@
 #include "fp32_forward.h"
 #include "layered_forward.h"
 #include "shadow_compare.h"
+#include "symmetry.h"
 #include "weight_image.h"
 #include "../../../include/gzero_nn.h"
 
@@ -1181,6 +1182,21 @@ extern "C" int gz_net_set_output_logits(gz_net* net, int on) {
     if (net->shadow) net->shadow->net->kp.logits = net->kp.logits;
     return 0;
 }
+
+// what symmetry.hip (the symmetry ensemble's entry points) may know of a net
+void gzsym::net_view(gz_net* net, gzsym::NetView* out) {
+    std::lock_guard<std::mutex> wl(net->wmu);
+    const gz_net_desc& d = net->d;
+    out->device = net->device;
+    out->plane_elems = d.input_channels * d.input_columns * d.input_rows;
+    out->roles = d.role_count;
+    out->num_values = d.num_values;
+    for (int r = 0; r < GZ_MAX_ROLES; ++r) out->policy[r] = r < d.role_count ? d.policy_dist_count[r] : 0;
+    out->logits = net->kp.logits;
+    out->host_stream = net->stream;
+}
+
+int gzsym::set_error(const std::string& msg) { return fail(msg); }
 
 extern "C" int gz_nn_compare_outputs(int device, int n, int roles, const int* policy_sizes, int num_values,
                                      const float* const* pol_a, const float* val_a, const float* const* pol_b,

@@ -1,0 +1,147 @@
+// Symmetry ensemble (include/gzero_nn.h gz_symmetry): a forward averaged over the S <= 8 elements of
+// a board's symmetry group.  With the caller's tables plane_src[s][E] and move_src[s][r][P_r], row r
+// of a call computes
+//
+//   X_s[i]  = X_r[plane_src[s][i]]                               sym_expand_kernel
+//   p_s, v_s = the net's ordinary forward of X_s                 gz_net_forward_device, S * rows rows
+//   out[m]  = (p_0[move_src[0][m]] + p_1[move_src[1][m]] + ...) * (1 / S)      sym_reduce_kernel
+//
+// in fp32 and in that order: acc starts as element 0's term, elements 1 .. S - 1 are added in
+// ascending order, and the scale is the exact product by 1 / S when S is a power of two and the
+// division acc / S otherwise.  Values are summed alike, without a permutation.  The forward is
+// batch-invariant, so a row's result depends on that row's planes and the tables alone.
+//
+// Scratch bound: one inner forward runs at most kMaxExpandedRows (2,048) expanded rows, so a call
+// goes through in chunks of chunk_rows(S) = 2,048 / S rows (256 rows for S = 8) and the object's
+// scratch holds at most 2,048 x (E + sum P_r + V) floats of expanded planes and raw outputs, plus
+// chunk_rows x (E + sum P_r + V) of staging for the host entry point -- 67 MB for amazons_10x10
+// (E = 1,200, P = 3,041 + 3,041), the largest game here.  GZ_SYM_CHUNK_ROWS in the environment lowers
+// the rows per chunk (tests), never raises them.
+//
+// The index arithmetic of both kernels and the table validation are plain / __host__ __device__
+// functions here, so that a CPU program can run them (tests/symmetry_host_check.cpp).
+#pragma once
+
+#include <cstddef>
+#include <cstdio>
+#include <string>
+#include <vector>
+
+#include "../../../include/gzero_nn.h"
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define GZSYM_HD __host__ __device__
+#else
+#define GZSYM_HD
+#endif
+
+namespace gzsym {
+
+constexpr int kMaxCount = 8;
+constexpr int kMaxExpandedRows = 2048;
+
+// Expanded rows are element-major: element s of row r of a chunk of n rows is row s * n + r.
+GZSYM_HD inline size_t expanded_row(int s, int r, int n) { return (size_t)s * (size_t)n + (size_t)r; }
+
+// sym_expand_kernel, output element o of [S * n][E]: where it reads in the chunk's planes [n][E].
+GZSYM_HD inline size_t expand_src(size_t o, int n, int E, const int* plane_src) {
+    const size_t row = o / (size_t)E;
+    const int i = (int)(o - row * (size_t)E);
+    const int s = (int)(row / (size_t)n);
+    const int r = (int)(row - (size_t)s * (size_t)n);
+    return (size_t)r * (size_t)E + (size_t)plane_src[(size_t)s * E + i];
+}
+
+// The outputs of one row, all roles then the values, as one index space [0, sum P_r + V).
+struct OutLayout {
+    int R, V, S;
+    int P[GZ_MAX_ROLES];
+    int total;                                   // sum P_r + V
+};
+
+// Column j of a row: role (R for the values) and index within it.
+GZSYM_HD inline void split_column(const OutLayout& L, int j, int* role, int* m) {
+    int r = 0;
+    while (r < L.R && j >= L.P[r]) { j -= L.P[r]; ++r; }
+    *role = r;
+    *m = j;
+}
+
+// sym_reduce_kernel, one output element: `raw` is the role's (or the values') raw outputs
+// [S * n][width], `src` the role's move table [S][width] (nullptr for the values).
+GZSYM_HD inline float reduce_one(const float* raw, const int* src, int S, int n, int r, int width, int m) {
+    float acc = raw[expanded_row(0, r, n) * (size_t)width + (size_t)(src ? src[m] : m)];
+    for (int s = 1; s < S; ++s)
+        acc += raw[expanded_row(s, r, n) * (size_t)width + (size_t)(src ? src[(size_t)s * width + m] : m)];
+    if ((S & (S - 1)) == 0) return acc * (1.0f / (float)S);
+    return acc / (float)S;
+}
+
+// Rows per chunk for S elements; env_rows > 0 (GZ_SYM_CHUNK_ROWS) lowers it.
+inline int chunk_rows(int S, int env_rows) {
+    int c = kMaxExpandedRows / (S < 1 ? 1 : S);
+    if (env_rows > 0 && env_rows < c) c = env_rows;
+    return c < 1 ? 1 : c;
+}
+
+// true when t[0 .. len) holds every value of 0 .. len - 1 once; else *bad = the first offending entry
+inline bool is_permutation(const int* t, int len, int* bad) {
+    std::vector<char> seen((size_t)len, 0);
+    for (int i = 0; i < len; ++i) {
+        if (t[i] < 0 || t[i] >= len || seen[(size_t)t[i]]) { *bad = i; return false; }
+        seen[(size_t)t[i]] = 1;
+    }
+    return true;
+}
+
+// Everything gz_symmetry_create checks, before any device call.  Returns "" or the refusal.
+inline std::string validate_tables(int count, int plane_elems, const int* plane_src, int roles,
+                                   const int* policy_sizes, const int* const* move_src) {
+    char b[200];
+    if (count < 1 || count > kMaxCount) {
+        snprintf(b, sizeof b, "symmetry: count %d outside 1..%d", count, kMaxCount);
+        return b;
+    }
+    if (plane_elems < 1 || roles < 1 || roles > GZ_MAX_ROLES) {
+        snprintf(b, sizeof b, "symmetry: plane_elems %d or roles %d out of range (roles 1..%d)", plane_elems, roles, GZ_MAX_ROLES);
+        return b;
+    }
+    if (!plane_src || !policy_sizes || !move_src) return "symmetry: null table";
+    for (int r = 0; r < roles; ++r) {
+        if (policy_sizes[r] < 1) {
+            snprintf(b, sizeof b, "symmetry: policy size %d of role %d out of range", policy_sizes[r], r);
+            return b;
+        }
+        if (!move_src[r]) return "symmetry: null table";
+    }
+    int bad = 0;
+    for (int s = 0; s < count; ++s) {
+        if (!is_permutation(plane_src + (size_t)s * plane_elems, plane_elems, &bad)) {
+            snprintf(b, sizeof b, "symmetry: plane table of element %d is not a permutation of 0..%d (entry %d = %d)", s,
+                     plane_elems - 1, bad, plane_src[(size_t)s * plane_elems + bad]);
+            return b;
+        }
+        for (int r = 0; r < roles; ++r)
+            if (!is_permutation(move_src[r] + (size_t)s * policy_sizes[r], policy_sizes[r], &bad)) {
+                snprintf(b, sizeof b, "symmetry: move table of element %d, role %d is not a permutation of 0..%d (entry %d = %d)",
+                         s, r, policy_sizes[r] - 1, bad, move_src[r][(size_t)s * policy_sizes[r] + bad]);
+                return b;
+            }
+    }
+    return "";
+}
+
+// What the ensemble needs to know of a net (gz_nn.hip defines both; gz_net is private to it).
+struct NetView {
+    int device;
+    int plane_elems;                             // C * H * W
+    int roles, num_values;
+    int policy[GZ_MAX_ROLES];
+    int logits;                                  // gz_net_set_output_logits mode, read under the net's lock
+    void* host_stream;                           // the stream of the net's synchronous host-buffer forward
+};
+void net_view(gz_net* net, NetView* out);
+int set_error(const std::string& msg);           // gz_nn_last_error's message; returns -1
+
+}  // namespace gzsym

@@ -266,6 +266,41 @@ int gz_nn_compare_outputs(int device, int n, int roles, const int* policy_sizes,
                           const float* const* pol_a, const float* val_a,
                           const float* const* pol_b, const float* val_b, gz_shadow_stats* out);
 
+/* ---- symmetry ensemble: a forward averaged over a board's symmetries ------------------------------
+ * A gz_symmetry holds the tables of a group of S = count <= 8 board symmetries, element 0 being the
+ * identity by convention (galvanise_zero_amd/util/symmetry.py builds them from a game's descriptor):
+ *   plane_src[s][i]     the planes of row X transformed by element s are X_s[i] = X[plane_src[s][i]],
+ *                       i over plane_elems = C * H * W;
+ *   move_src[r][s][m]   move m of role r is move move_src[r][s][m] in the transformed position.
+ * gz_net_forward_sym computes, for every row, the net's ordinary forward (its own arithmetic mode) of
+ * the S transformed rows -> p_s, v_s, and then in fp32, in this order,
+ *   acc = p_0[move_src[0][m]];  acc += p_s[move_src[s][m]] for s = 1 .. S - 1;
+ *   out[m] = acc * (1 / S) when S is a power of two (exact), else acc / S;
+ * values alike without a permutation.  A row's result depends on its planes and the tables alone --
+ * not on n, on how the call chunks its rows, or on the entry point -- and count = 1 with identity
+ * tables is gz_net_forward bit for bit.  Non-finite values propagate.  Two kernels
+ * (csrc/nn/symmetry.hip) expand the planes and reduce the outputs around one gz_net_forward_device
+ * of S * rows rows, in chunks of 2,048 / S rows through scratch the gz_symmetry owns (the bound:
+ * csrc/nn/symmetry.h; GZ_SYM_CHUNK_ROWS in the environment lowers the rows per chunk).  A net's shadow
+ * check sees the inner forward as one more forward.
+ * Refusals ("symmetry: ..."): gz_symmetry_create -- count outside 1..8, a plane or move table that is
+ * not a permutation (the message names the element and the role); tables are copied and everything
+ * is validated before any device call (the device is first touched by a forward).  A forward -- tables
+ * whose plane_elems, roles or policy sizes are not the net's, and a net in gz_net_set_output_logits
+ * mode (an average of logits is not what this computes). */
+typedef struct gz_symmetry gz_symmetry;
+gz_symmetry* gz_symmetry_create(int device, int count, int plane_elems, const int* plane_src /*[count][plane_elems]*/,
+                                int roles, const int* policy_sizes, const int* const* move_src /*[roles] -> [count][P_r]*/);
+void gz_symmetry_destroy(gz_symmetry* s);
+int gz_symmetry_count(const gz_symmetry* s);
+/* Synchronous, host buffers as gz_net_forward; takes the net's weight lock as gz_net_forward does and
+ * runs on the net's own stream. */
+int gz_net_forward_sym(gz_net* net, gz_symmetry* s, const float* planes, int n, float* const* policies, float* values);
+/* Asynchronous on the caller's stream, device (or pinned host) buffers as gz_net_forward_device.  The
+ * scratch belongs to the gz_symmetry: one gz_symmetry serves one stream at a time. */
+int gz_net_forward_sym_device(gz_net* net, gz_symmetry* s, void* stream, const float* d_planes, int n,
+                              float* const* d_policies, float* d_values);
+
 /* Diagnostics: with GZ_KERNEL_STAMPS set in the environment, gz_net_forward records per-workgroup
  * s_memtime stamps at phase boundaries; out8[0] = workgroups averaged, out8[1..4] = their mean
  * cycles of (input + initial conv, residual trunk, head 1x1 convs + features, fused dense heads)
