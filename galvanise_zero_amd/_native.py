@@ -103,6 +103,9 @@ def canonical_precision(precision):
     return _CANONICAL[PRECISIONS[precision]]
 
 
+# HipNet.heads_path() bits (include/gzero_nn.h GZ_HEADS_*)
+HEADS_FUSED_SMALL, HEADS_FUSED_LARGE, HEADS_SEQ, HEADS_GEMM, HEADS_LONG_ROW = 1, 2, 4, 8, 16
+
 _FP = ctypes.POINTER(ctypes.c_float)
 _IP = ctypes.POINTER(ctypes.c_int)
 GZ_MAX_SEGMENTS = 32
@@ -164,6 +167,9 @@ def nn_lib():
         lib.gz_net_flops_per_eval.argtypes = [ctypes.c_void_p]
         lib.gz_net_heads_fused.restype = ctypes.c_int
         lib.gz_net_heads_fused.argtypes = [ctypes.c_void_p]
+        if hasattr(lib, "gz_net_heads_path"):   # (absent from older A/B builds loaded through GZ_LIB_DIR)
+            lib.gz_net_heads_path.restype = ctypes.c_int
+            lib.gz_net_heads_path.argtypes = [ctypes.c_void_p]
         lib.gz_net_set_output_logits.argtypes = [ctypes.c_void_p, ctypes.c_int]
         lib.gz_net_kernel_name.restype = ctypes.c_char_p
         lib.gz_net_kernel_name.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -455,6 +461,12 @@ class HipNet(object):
     def heads_fused(self):
         """True when the large trunk variant runs the dense heads itself (no heads_kernel launch)."""
         return bool(self.lib.gz_net_heads_fused(self.handle))
+
+    def heads_path(self):
+        """The code paths the dense heads of this net take, an OR of the HEADS_* bits (gz_net_heads_path,
+        include/gzero_nn.h): fused into the small / the large trunk variant, the sequential LDS row,
+        the policy GEMM, a policy longer than the GEMM logits' register softmax."""
+        return int(self.lib.gz_net_heads_path(self.handle))
 
     def close(self):
         if self.handle:

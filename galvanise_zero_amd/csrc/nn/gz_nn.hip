@@ -623,6 +623,11 @@ extern "C" void gz_net_destroy(gz_net* net) {
 extern "C" size_t gz_net_weight_count(const gz_net* net) { return net ? net->nweights : 0; }
 
 extern "C" int gz_net_heads_fused(const gz_net* net) { return net->large.fused_heads ? 1 : 0; }
+extern "C" int gz_net_heads_path(const gz_net* net) {
+    return (net->small.fused_heads ? GZ_HEADS_FUSED_SMALL : 0) | (net->large.fused_heads ? GZ_HEADS_FUSED_LARGE : 0) |
+           (net->kp.heads_seq ? GZ_HEADS_SEQ : 0) | (net->gemm_heads ? GZ_HEADS_GEMM : 0) |
+           (net->kp.maxP > kGemmSoftmaxMax ? GZ_HEADS_LONG_ROW : 0);
+}
 
 extern "C" double gz_net_flops_per_eval(const gz_net* net) {
     const gz_net_desc& d = net->d;   // = NetDesc.flops_per_eval (desc.py)

@@ -206,6 +206,25 @@ double gz_net_flops_per_eval(const gz_net* net);
  * kernels: no separate heads launch), 0 when a separate heads kernel follows it. */
 int gz_net_heads_fused(const gz_net* net);
 
+/* Which of their code paths the dense heads of this net take (read-only; decided at gz_net_create
+ * from the geometry, the mode and the LDS budget): an OR of
+ *   GZ_HEADS_FUSED_SMALL  the small trunk variant (launches below gz_net_large_min_rows) runs the heads itself
+ *   GZ_HEADS_FUSED_LARGE  the large trunk variant does (what gz_net_heads_fused returns)
+ *   GZ_HEADS_SEQ          one Dense after another with a max(P, VH) LDS row: the two-phase row
+ *                         [P4_0 | .. | VH4] would push a kernel past the 160 KB of LDS
+ *   GZ_HEADS_GEMM         the policy Denses run as one MFMA GEMM per launch (no fused heads, largest
+ *                         policy >= 512, not fp32-ieee / fp16x3-layered)
+ *   GZ_HEADS_LONG_ROW     the largest policy exceeds the register softmax of the GEMM logits (3,072):
+ *                         with GZ_HEADS_GEMM, such roles' softmax goes through LDS, one role at a time
+ * For tests and diagnostics: a test names the path it is about and asserts it here, so that it
+ * cannot stop covering that path unnoticed when a budget constant moves. */
+#define GZ_HEADS_FUSED_SMALL 1
+#define GZ_HEADS_FUSED_LARGE 2
+#define GZ_HEADS_SEQ 4
+#define GZ_HEADS_GEMM 8
+#define GZ_HEADS_LONG_ROW 16
+int gz_net_heads_path(const gz_net* net);
+
 const char* gz_nn_last_error(void);
 
 /* ---- shadow check: live forwards against a second arithmetic mode --------------------------------

@@ -7,7 +7,10 @@ arithmetic a mode uses, every correctly rounded operation is exact in any order,
 correct kernel returns the oracle's logits exactly.  lattice_weights / lattice_planes build such nets,
 check_representable asserts the conditions under which that is a theorem, expected_logits is the
 oracle (oracle/nn_ref.forward) snapped to the lattice, and faulty_logits applies a kernel-like slip
-to the oracle side so that the CPU suite can show the comparison would notice it.
+to the oracle side so that the CPU suite can show the comparison would notice it (faulty_se_logits:
+the slips of a squeeze-excite kernel; faulty_head_logits: those of the dense heads, with
+head_liveness, the conditions under which no output of a launch could pass against an untouched or
+a neighbour's buffer).
 
 How the BN fold is made exact: galvanise_zero_amd/csrc/nn/weight_image.h fold_element computes
 scale = gamma / sqrt(fl32(var + 1e-3f)) in float32.  exact_vars() searches the float32 var for which
@@ -887,3 +890,148 @@ def faulty_logits(desc, weights, planes, fault, conv, bits=8):
             assert fault == "wrap_pad", fault
         return inp, k, fault == "wrap_pad"
     return _forward(desc, weights, planes, hooks={conv: hook})[0]
+
+
+# ---- the dense heads: faults on the oracle side only -------------------------------------------------
+HEAD_FAULTS = ("role_features_slip", "logit_offset_padding", "dense_row_stride", "drop_last_group4", "drop_last_tile16",
+               "drop_last_k", "drop_last_hidden", "bias_from_other_role", "value_swap")
+
+
+def head_last_rows(desc, weights):
+    """The same weights with the last row of every head Dense made to count, without a random draw
+    (the generator's sparse Denses seldom reach it): policy r's last output reads the last of its
+    features, the last value hidden unit reads the last value feature, and every value output reads
+    the last hidden unit -- each with a +1 where the generator left a 0.  A dropped last k, a dropped
+    last hidden unit or a Dense whose padded last k-tile is misread then has something to lose."""
+    out = []
+    for name, a in weights:
+        if name.endswith("_dense") and name.startswith("policy") or name == "value_hidden":
+            a = a.copy()
+            a[-1, -1] = a[-1, -1] or 1.0
+        elif name == "value_dense":
+            a = a.copy()
+            a[-1] = np.where(a[-1] == 0, 1.0, a[-1])
+        out.append((name, a))
+    return out
+
+
+def head_operands(desc, weights, planes):
+    """{Dense name: (inputs [N, K], kernel [K, n], bias [n])} of the clean walk, float64."""
+    seen = {}
+
+    def tap(kind, name, inp, k, bn, skip):
+        if kind in ("dense", "gemm"):
+            seen[name] = (inp, k, bn)
+    _forward(desc, weights, planes, tap=tap)
+    return seen
+
+
+def head_fault_roles(desc, weights, fault):
+    """The outputs (role indices; role_count: the value output) that a head fault touches on this net,
+    from the geometry and the weights alone; [] where the fault cannot occur:
+      role_features_slip, bias_from_other_role   roles 1.. of a net with at least two roles
+      logit_offset_padding   roles behind one whose P is no multiple of 4 (elsewhere P and P4 offsets agree)
+      dense_row_stride, drop_last_group4   roles whose P is no multiple of 4 (elsewhere P4 = P, no partial group)
+      drop_last_tile16       every role
+      drop_last_k            roles whose Dense reads its last feature (head_last_rows: all), and the value output
+      drop_last_hidden       the value output
+      value_swap             the value output of a net with at least two values"""
+    R, P = desc.role_count, list(desc.policy_dist_count)
+    assert fault in HEAD_FAULTS, fault
+    if fault in ("role_features_slip", "bias_from_other_role"):
+        return list(range(1, R))
+    if fault == "logit_offset_padding":
+        return [r for r in range(1, R) if any(p % 4 for p in P[:r])]
+    if fault in ("dense_row_stride", "drop_last_group4"):
+        return [r for r in range(R) if P[r] % 4]
+    if fault == "drop_last_tile16":
+        return list(range(R))
+    w = dict(weights)
+    if fault == "drop_last_k":
+        return [r for r in range(R) if w["policy%d_dense" % r][-1].any()] + ([R] if w["value_hidden"][-1].any() else [])
+    if fault == "drop_last_hidden":
+        return [R] if w["value_dense"][-1].any() else []
+    return [R] if desc.num_values >= 2 else []
+
+
+def faulty_head_logits(desc, weights, planes, fault):
+    """The logits of a forward whose dense heads slip the way a wrong kernel or packer would (oracle
+    side only; the trunk and the heads' 1 x 1 convs are the clean walk's):
+      role_features_slip     role r reads role r - 1's features
+      logit_offset_padding   the boards' logit rows are laid out with one padding (every role's P rounded
+                             up to 4, as in the LDS row; or none, as in the policy GEMM's scratch) and
+                             read back with the other's offsets; padding holds 0, as does what lies past
+                             the last board
+      dense_row_stride       the Dense weights, stored [K][P4], are read with a row stride of P
+      drop_last_group4       the outputs of the last partial group of 4 are never written (0)
+      drop_last_tile16       the outputs of the last tile of 16 are never written (0)
+      drop_last_k            the last feature of every policy Dense and of the value hidden Dense is left out
+      drop_last_hidden       the last value hidden unit is left out of the value Dense
+      bias_from_other_role   role r's bias of column j is role r - 1's (column j mod its P)
+      value_swap             value outputs 0 and 1 change places"""
+    assert fault in HEAD_FAULTS, fault
+    R, P = desc.role_count, list(desc.policy_dist_count)
+    ops = head_operands(desc, weights, planes)
+    pol = [ops["policy%d_dense" % r] for r in range(R)]
+    outs = [x @ k + b for x, k, b in pol]
+    xh, kh, bh = ops["value_hidden"]
+    xv, kv, bv = ops["value_dense"]
+    value = xv @ kv + bv
+    N = planes.shape[0]
+    if fault == "role_features_slip":
+        outs = [outs[0]] + [pol[r - 1][0] @ pol[r][1] + pol[r][2] for r in range(1, R)]
+    elif fault == "logit_offset_padding":
+        P4 = [(p + 3) & ~3 for p in P]
+        for stored, read in ((P4, P), (P, P4)):
+            buf = np.zeros((N + 1) * sum(stored))
+            for r in range(R):
+                for b in range(N):
+                    at = b * sum(stored) + sum(stored[:r])
+                    buf[at:at + P[r]] = outs[r][b]
+            got = [np.stack([buf[b * sum(stored) + sum(read[:r]):][:P[r]] for b in range(N)]) for r in range(R)]
+            if stored is P4:
+                lds = got
+        # (either direction of the slip: the one shown is the LDS row's, read with the GEMM scratch's offsets,
+        # unless only the other moves something)
+        outs = lds if any(not np.array_equal(a, b) for a, b in zip(lds, outs)) else got
+    elif fault == "dense_row_stride":
+        for r in range(R):
+            x, k, b = pol[r]
+            kp = np.zeros((k.shape[0], (P[r] + 3) & ~3))
+            kp[:, :P[r]] = k
+            outs[r] = x @ kp.reshape(-1)[:k.shape[0] * P[r]].reshape(k.shape[0], P[r]) + b
+    elif fault in ("drop_last_group4", "drop_last_tile16"):
+        g = 4 if fault == "drop_last_group4" else 16
+        for r in range(R):
+            if fault == "drop_last_tile16" or P[r] % g:
+                outs[r] = outs[r].copy()
+                outs[r][:, (P[r] - 1) // g * g:] = 0.0
+    elif fault == "drop_last_k":
+        outs = [x[:, :-1] @ k[:-1] + b for x, k, b in pol]
+        hid = nn_ref._act(xh[:, :-1] @ kh[:-1] + bh, False)
+        value = hid @ kv + bv
+    elif fault == "drop_last_hidden":
+        value = xv[:, :-1] @ kv[:-1] + bv
+    elif fault == "bias_from_other_role":
+        outs = [outs[0]] + [pol[r][0] @ pol[r][1] + pol[r - 1][2][np.arange(P[r]) % P[r - 1]] for r in range(1, R)]
+    elif fault == "value_swap" and desc.num_values >= 2:
+        value = value.copy()
+        value[:, [0, 1]] = value[:, [1, 0]]
+    return outs + [value]
+
+
+def head_liveness(expected):
+    """What the expected logits of a launch must be for the comparison with a device buffer to mean
+    something, as a list of violations (empty: alive): every output of every row holds a nonzero
+    entry; no two rows of the launch are equal in any output; every policy column and every value
+    output is nonzero in some row (an output that is identically 0 would pass against an untouched
+    buffer)."""
+    bad = []
+    for i, z in enumerate(expected):
+        if not (z != 0).any(axis=1).all():
+            bad.append((i, "a row of zeros"))
+        if len(np.unique(z, axis=0)) != len(z):
+            bad.append((i, "two equal rows"))
+        if not (z != 0).any(axis=0).all():
+            bad.append((i, "%d columns that are 0 in every row" % int((~(z != 0).any(axis=0)).sum())))
+    return bad

@@ -4,7 +4,9 @@ check_representable); the nets are alive; and the comparison would notice a wron
 kernel-like slip, applied to the oracle side alone, moves at least one expected logit.  For the
 squeeze-excite nets that includes the saturation conditions (every gate exactly 0, 1/2 or 1), gates
 that take all three values and differ between the boards of a launch, and the slips a squeeze-excite
-kernel can make (exact_lattice.SE_FAULTS).  No GPU."""
+kernel can make (exact_lattice.SE_FAULTS).  For the dense-heads nets (HEAD_CASES): no output of a
+launch is zero where an untouched buffer would pass, and each slip a heads kernel can make
+(exact_lattice.HEAD_FAULTS) moves a logit wherever the net's geometry lets it occur.  No GPU."""
 import dataclasses
 
 import numpy as np
@@ -13,7 +15,8 @@ import pytest
 import exact_lattice as xl
 from galvanise_zero_amd.nn.desc import NetDesc
 from oracle import nn_ref
-from test_nn_exact_gpu import ALL, CASES, CHUNKED, LARGE_ROWS, PROBABILITY, SCALES, SE_CASES, SE_VARIED, build
+from test_nn_exact_gpu import (ALL, CASES, CHUNKED, HEAD_CASES, HEAD_CHUNKED, HEAD_LARGE_VARIANTS, HEAD_NO_GEMM, HEAD_VARIED,
+                               LARGE_ROWS, PROBABILITY, SAT, SATURATED, SCALES, SE_CASES, SE_VARIED, _softmax64, build, saturated)
 
 FAMILIES = {c.family: name for name, c in CASES.items() if c.family}
 GEOMETRY_FAULTS = ("tap_swap", "wrap_pad", "channel_swap", "drop_last_channel")
@@ -184,7 +187,8 @@ def test_liveness(name):
     assert desc.residual_layers < 6
     assert xl.trunk_alive(desc, w, x) >= 0.30
     for z in expected[:-1]:
-        assert len(np.unique(z)) >= 32
+        # (a head case's role of fewer than 32 columns: test_head_liveness)
+        assert len(np.unique(z)) >= 32 or (name in HEAD_CASES and z.shape[1] < 32)
     assert len(np.unique(expected[-1])) > 1
     if name in SE_CASES:
         _se_liveness(desc, w, x)
@@ -298,3 +302,103 @@ def test_every_mode_and_family_is_run():
         assert '"%s"' % mode in section or "`\"%s\"`" % mode in section, mode
     assert {m for _, m in PROBABILITY} == set(ALL)
     assert len(FAMILIES) >= 9 + len(SE_FAMILIES) and len(SE_FAMILIES) == 8
+
+
+# ---- the dense heads ---------------------------------------------------------------------------------
+def _head_fault_applies(name, fault):
+    """Where a head fault can occur at all (exact_lattice.head_fault_roles has the outputs it touches):
+    a neighbour's features or bias need a second role; an offset computed with the other path's
+    padding, a row stride of P for P4 and a dropped partial group of 4 need a role whose size is no
+    multiple of 4 (for the offset: in front of another role); swapped value outputs need two values.
+    The last tile of 16, the last k and the last hidden unit exist on every net (head_last_rows makes
+    every Dense read its last input)."""
+    desc, w, _, _ = build(name)
+    return bool(xl.head_fault_roles(desc, w, fault))
+
+
+@pytest.mark.parametrize("name", sorted(HEAD_CASES))
+def test_head_liveness(name):
+    """On the largest launch of every head case: every role's logits and the value logits hold a
+    nonzero entry in every row, no two rows are equal in any output, and every policy column and
+    every value output is nonzero in some row -- a P = 1 role and a V = 1 value in every row."""
+    c = CASES[name]
+    desc, w, x, expected = build(name)
+    assert c.head and x.shape[0] == max(c.rows or (1, 3)) and set(c.path) >= set(c.modes)
+    assert xl.head_liveness(expected) == []
+    for z in expected:
+        if z.shape[1] == 1:
+            assert (z != 0).all()
+    wd = dict(w)
+    for r in range(desc.role_count):
+        assert wd["policy%d_dense" % r][-1, -1] != 0
+    assert wd["value_hidden"][-1, -1] != 0 and (wd["value_dense"][-1] != 0).all()
+
+
+def test_head_cases_cover_the_parameter_space():
+    """Role counts 1 to 4, value counts 1 to 4, hidden widths of 6 and above 256 that are no multiple
+    of 4, a sigmoid and a pooling value head, every heads_path the kernels can take, and the
+    launches whose last heads workgroup (5 rows) and last GEMM board tile (65 rows) are partial."""
+    descs = [c.desc for c in HEAD_CASES.values()]
+    assert {d.role_count for d in descs} == {1, 2, 3, 4} and {d.num_values for d in descs} == {1, 2, 3, 4}
+    vh = {d.value_hidden_size for d in descs}
+    assert 6 in vh and any(v > 256 and v % 4 and v % 64 for v in vh)
+    assert any(d.value_sigmoid for d in descs) and any(d.global_pooling_value and xl.sig_bits(float(d.hw)) == 1 for d in descs)
+    assert any(1 in d.policy_dist_count for d in descs) and any(3072 in d.policy_dist_count for d in descs)
+    paths = {bits for c in HEAD_CASES.values() for mode, bits in c.path.items() if mode in c.modes}
+    assert paths == {0, 3, 8, 16, 24, 3 | 16, 3 | 4 | 16}
+    assert any(c.rows and 5 in c.rows for c in HEAD_CASES.values()) and any(c.rows and 65 in c.rows for c in HEAD_CASES.values())
+    for name in (HEAD_VARIED, HEAD_CHUNKED, HEAD_NO_GEMM) + tuple(n for n, _, _ in HEAD_LARGE_VARIANTS):
+        assert build(name)[2].shape[0] >= 5
+
+
+@pytest.mark.parametrize("name,fault", [(name, fault) for name in sorted(HEAD_CASES) for fault in xl.HEAD_FAULTS])
+def test_head_fault_is_seen(name, fault):
+    """Each slip a heads kernel can make, on the oracle side alone, moves an expected logit of every
+    output it touches (exact_lattice.faulty_head_logits), on every head case where it can occur."""
+    if not _head_fault_applies(name, fault):
+        return
+    desc, w, x, expected = build(name)
+    got = xl.faulty_head_logits(desc, w, x, fault)
+    for r in xl.head_fault_roles(desc, w, fault):
+        assert not np.array_equal(got[r], expected[r]), (name, fault, r)
+    clean = xl.head_operands(desc, w, x)
+    for r in range(desc.role_count):      # (the operands the faults are applied to are the walk's own)
+        xr, k, b = clean["policy%d_dense" % r]
+        assert np.array_equal(xr @ k + b, expected[r])
+
+
+def test_head_faults_cover_the_cases():
+    """Every fault occurs on most cases; the ones that need unequal padding or two values on at least five."""
+    for fault in xl.HEAD_FAULTS:
+        on = [name for name in HEAD_CASES if _head_fault_applies(name, fault)]
+        assert len(on) >= (len(HEAD_CASES) if fault in ("drop_last_tile16", "drop_last_k", "drop_last_hidden") else 5), (fault, on)
+
+
+@pytest.mark.parametrize("tie", (False, True), ids=("one", "tie"))
+@pytest.mark.parametrize("name,mode", SATURATED)
+def test_saturated_conditions(name, mode, tie):
+    """The saturated nets still meet the mode's conditions; the raised logits stand at least 2^11 above
+    every other of their row (so float32's exp of the difference is 0, as float64's is), and the
+    float64 softmax / sigmoid of the expected logits is exactly the 1, 0.5 and 0 the GPU test asserts."""
+    desc, w, x, expected, probs = saturated(name, tie)
+    xl.check_representable(desc, w, x, mode)
+    for i, (z, p) in enumerate(zip(expected, probs)):
+        if i == desc.role_count and desc.value_sigmoid:
+            with np.errstate(over="ignore"):
+                assert np.array_equal(1.0 / (1.0 + np.exp(-z)), p)
+            continue
+        assert np.array_equal(_softmax64(z), p), (name, i)
+        low = np.where(p > 0, -np.inf, z).max(axis=1)
+        assert (z.max(axis=1) - low >= SAT / 2).all()
+
+
+def test_heads_path_bits_match_the_header():
+    """_native's HEADS_* are include/gzero_nn.h's GZ_HEADS_*."""
+    import os
+    import re
+    from galvanise_zero_amd import _native
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "gzero_nn.h")).read()
+    bits = {name: int(value) for name, value in re.findall(r"#define GZ_(HEADS_\w+) (\d+)", header)}
+    assert len(bits) == 5 and sorted(bits.values()) == [1, 2, 4, 8, 16]
+    for name, value in bits.items():
+        assert getattr(_native, name) == value
