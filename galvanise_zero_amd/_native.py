@@ -202,6 +202,13 @@ def nn_lib():
             lib.gz_net_forward_sym.argtypes = [ctypes.c_void_p, ctypes.c_void_p, _FP, ctypes.c_int, ctypes.POINTER(_FP), _FP]
             lib.gz_net_forward_sym_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                       ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]
+        if hasattr(lib, "gz_net_forward_sym_pick"):   # (absent from older A/B builds loaded through GZ_LIB_DIR)
+            lib.gz_net_forward_sym_pick.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint, _FP, ctypes.c_int,
+                                                    ctypes.POINTER(_FP), _FP]
+            lib.gz_net_forward_sym_pick_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p,
+                                                           ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
+                                                           ctypes.c_void_p]
+            lib.gz_symmetry_picks.argtypes = [ctypes.c_void_p, ctypes.c_uint, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, _IP]
         lib._gz_typed = True
     return lib
 
@@ -355,9 +362,12 @@ class HipNet(object):
         forward(X, symmetry=...); that the tables fit this net is checked by the forward."""
         return HipSymmetry(tables.plane_src, tables.move_src, self.device)
 
-    def forward(self, planes, symmetry=None):
+    def forward(self, planes, symmetry=None, pick=None):
         """symmetry: None, or a HipSymmetry (make_symmetry): the forward averaged over its board
-        symmetries (gz_net_forward_sym, include/gzero_nn.h)."""
+        symmetries (gz_net_forward_sym, include/gzero_nn.h).  pick: None for that ensemble, or a
+        32-bit salt: each row evaluated under ONE element of the tables, hashed on the GPU from the
+        row's own planes and the salt, its policies mapped back (gz_net_forward_sym_pick) -- one
+        forward, bit for bit the plain forward of the permuted row read through the move table."""
         d = self.desc
         planes = np.ascontiguousarray(planes, dtype=np.float32)
         n = planes.shape[0]
@@ -365,6 +375,12 @@ class HipNet(object):
         pols = [np.empty((n, p), dtype=np.float32) for p in d.policy_dist_count]
         val = np.empty((n, d.num_values), dtype=np.float32)
         arr = (_FP * len(pols))(*[_fptr(p) for p in pols])
+        if pick is not None:
+            if symmetry is None:
+                raise ValueError("pick=%r needs symmetry=" % (pick,))
+            self._check(self.lib.gz_net_forward_sym_pick(self.handle, symmetry.handle, int(pick) & 0xFFFFFFFF, _fptr(planes), n, arr,
+                                                         _fptr(val)), "gz_net_forward_sym_pick")
+            return pols + [val]
         if symmetry is not None:
             self._check(self.lib.gz_net_forward_sym(self.handle, symmetry.handle, _fptr(planes), n, arr, _fptr(val)),
                         "gz_net_forward_sym")
@@ -387,6 +403,29 @@ class HipNet(object):
         self._check(self.lib.gz_net_forward_sym_device(self.handle, symmetry.handle, ctypes.c_void_p(stream),
                                                        ctypes.c_void_p(d_planes), n, arr, ctypes.c_void_p(d_values)),
                     "gz_net_forward_sym_device")
+
+    def forward_sym_pick_device(self, symmetry, salt, stream, d_planes, n, d_policies, d_values):
+        """gz_net_forward_sym_pick_device: one symmetry per row on `stream`, device pointers as
+        forward_device.  One HipSymmetry serves one stream at a time (its scratch)."""
+        arr = (ctypes.c_void_p * len(d_policies))(*d_policies)
+        self._check(self.lib.gz_net_forward_sym_pick_device(self.handle, symmetry.handle, int(salt) & 0xFFFFFFFF,
+                                                            ctypes.c_void_p(stream), ctypes.c_void_p(d_planes), n, arr,
+                                                            ctypes.c_void_p(d_values)),
+                    "gz_net_forward_sym_pick_device")
+
+    def symmetry_picks(self, symmetry, salt, planes=None, device_ptr=None, n=None):
+        """The element g of each row as the GPU kernel hashes it (gz_symmetry_picks): planes a host
+        array [n, ...], or device_ptr + n.  util.symmetry.pick_elements is the numpy statement."""
+        if planes is not None:
+            planes = np.ascontiguousarray(planes, dtype=np.float32)
+            n, ptr, dev = planes.shape[0], planes.ctypes.data, 0
+            assert planes.size == n * symmetry.plane_src.shape[1]
+        else:
+            ptr, dev = device_ptr, 1
+        out = np.empty(n, dtype=np.int32)
+        self._check(self.lib.gz_symmetry_picks(symmetry.handle, int(salt) & 0xFFFFFFFF, dev, ctypes.c_void_p(ptr), n,
+                                               out.ctypes.data_as(_IP)), "gz_symmetry_picks")
+        return out
 
     def forward_segments(self, stream, segments):
         """Asynchronous segmented launch on `stream`: segments = [(rows, planes_ptr, [policy_ptr per
@@ -750,6 +789,10 @@ def runner_lib():
         lib.gz_runner_roll_info.argtypes = [_VP, ctypes.POINTER(ctypes.c_long), ctypes.c_int,
                                             ctypes.POINTER(ctypes.c_long)]
         lib.gz_runner_ordinal_stats.argtypes = [_VP, ctypes.POINTER(GzOrdinalStats)]
+        if hasattr(lib, "gz_runner_set_symmetry"):   # (absent from older A/B builds loaded through GZ_LIB_DIR)
+            lib.gz_runner_set_symmetry.argtypes = [_VP, _VP, ctypes.c_uint]
+            lib.gz_runner_sym_pick_rows.restype = ctypes.c_long
+            lib.gz_runner_sym_pick_rows.argtypes = [_VP]
         lib._gz_runner_typed = True
     return lib
 

@@ -14,6 +14,7 @@
 // planes itself (no staging copy; round 1).
 #include "../../../include/gzero_engine.h"
 #include "../../../include/gzero_nn.h"
+#include "symmetry.h"
 
 #include <hip/hip_runtime.h>
 
@@ -69,6 +70,12 @@ struct Batch {
     size_t d_cap = 0;                // rows d_planes holds
     float* d_out = nullptr;          // output staging: the batch's policies and values in HBM
     size_t d_out_cap = 0;            // rows d_out holds
+    // one symmetry per row (gz_runner_set_symmetry): the permuted planes the forward reads, each
+    // row's element, and the forward's raw outputs [role][rows][P_r], [rows][V] before the gather
+    float* d_sym_planes = nullptr;
+    int* d_picks = nullptr;
+    float* d_raw = nullptr;
+    size_t d_sym_cap = 0;            // rows the three hold
     std::vector<Part> parts;
     int rows = 0;
 };
@@ -108,6 +115,11 @@ struct gz_runner {
     bool out_staging = false;
     hipStream_t out_stream = nullptr;
     int out_row_floats = 0;
+    // gz_runner_set_symmetry: every launch's rows evaluated under one table element each, picked on
+    // the GPU from the row's planes (csrc/nn/symmetry.h); null: none of it
+    gz_symmetry* sym = nullptr;
+    unsigned sym_salt = 0;
+    std::atomic<long> sym_rows{0};   // rows that went through the pick path
     Compose compose = kSplit;
     Batch batches_ring[2];
 
@@ -288,7 +300,7 @@ static void launcher_main(gz_runner* r) {
     std::deque<int> inflight;        // indices into batches_ring, oldest first
     int next_slot = 0;
     long launches_issued = 0;
-    std::vector<gz_segment> segs, hsegs;
+    std::vector<gz_segment> segs, hsegs, dsegs;
     while (true) {
         // retire finished batches (in order: one stream)
         while (!inflight.empty()) {
@@ -324,6 +336,7 @@ static void launcher_main(gz_runner* r) {
             r->segments.fetch_add((long)b.parts.size(), std::memory_order_relaxed);
             if (b.parts.front().row0 > 0 || !b.parts.back().last) r->split_launches.fetch_add(1, std::memory_order_relaxed);
             r->rows.fetch_add(b.rows, std::memory_order_relaxed);
+            if (r->sym) r->sym_rows.fetch_add(b.rows, std::memory_order_relaxed);
             r->batches.fetch_add(1, std::memory_order_relaxed);
             inflight.pop_front();
             r->cv.notify_all();
@@ -532,6 +545,35 @@ static void launcher_main(gz_runner* r) {
                 set_failed(r, "plane copy event failed");
                 return;
             }
+            if (r->sym) {
+                // the staged rows are contiguous in d_planes, in segment order: hash and permute them
+                // all in one launch; the forward reads the permuted copy
+                if (b.d_sym_cap < (size_t)b.rows) {
+                    if (b.d_sym_planes) (void)hipFree(b.d_sym_planes);
+                    if (b.d_picks) (void)hipFree(b.d_picks);
+                    if (b.d_raw) (void)hipFree(b.d_raw);
+                    b.d_sym_planes = b.d_raw = nullptr;
+                    b.d_picks = nullptr;
+                    b.d_sym_cap = 0;
+                    const size_t cap = std::max((size_t)b.rows, (size_t)4096);
+                    if (hipMalloc((void**)&b.d_sym_planes, cap * row_floats * 4) != hipSuccess ||
+                        hipMalloc((void**)&b.d_picks, cap * sizeof(int)) != hipSuccess ||
+                        hipMalloc((void**)&b.d_raw, cap * r->out_row_floats * 4) != hipSuccess) {
+                        set_failed(r, "device symmetry staging allocation failed");
+                        return;
+                    }
+                    b.d_sym_cap = cap;
+                }
+                if (gzsym::pick_expand_launch(r->sym, r->stream, r->sym_salt, b.d_planes, b.rows, b.d_picks, b.d_sym_planes) != 0) {
+                    set_failed(r, std::string("symmetry pick launch failed: ") + gz_nn_last_error());
+                    return;
+                }
+                size_t soff = 0;
+                for (gz_segment& sg : segs) {
+                    sg.planes = b.d_sym_planes + soff * row_floats;
+                    soff += sg.rows;
+                }
+            }
         }
         if (r->out_staging) {
             // the segments' outputs to this slot's HBM staging, [segment][policy 0 .. R-1, value]
@@ -557,10 +599,44 @@ static void launcher_main(gz_runner* r) {
                 off += (size_t)sg.rows * r->num_values;
             }
         }
+        const float* raw[GZ_MAX_ROLES + 1];
+        if (r->sym) {
+            // the forward writes raw outputs, [role][rows][P_r] then [rows][V] over the whole launch;
+            // the gather below reads them through each row's move table into the d_out blocks
+            dsegs = segs;
+            float* p = b.d_raw;
+            for (int j = 0; j < r->num_policies; ++j) {
+                raw[j] = p;
+                p += (size_t)b.rows * r->policy_sizes[j];
+            }
+            raw[r->num_policies] = p;
+            size_t row = 0;
+            for (gz_segment& sg : segs) {
+                for (int j = 0; j < r->num_policies; ++j) sg.policies[j] = (float*)raw[j] + row * r->policy_sizes[j];
+                sg.values = (float*)raw[r->num_policies] + row * r->num_values;
+                row += sg.rows;
+            }
+        }
         if (hipEventRecord(b.ev0, r->stream) != hipSuccess ||
             gz_net_forward_segments_ev(r->net, r->stream, segs.data(), (int)segs.size(), b.evm) != 0) {
             set_failed(r, std::string("launch failed: ") + gz_nn_last_error());
             return;
+        }
+        if (r->sym) {
+            gzsym::PickSegments ps{};
+            ps.nseg = (int)dsegs.size();
+            int row = 0;
+            for (size_t k = 0; k < dsegs.size(); ++k) {
+                ps.row0[k] = row;
+                row += dsegs[k].rows;
+                for (int j = 0; j < r->num_policies; ++j) ps.out[k][j] = dsegs[k].policies[j];
+                ps.out[k][r->num_policies] = dsegs[k].values;
+            }
+            if (gzsym::pick_gather_launch(r->sym, r->stream, b.d_picks, b.rows, raw, ps) != 0) {
+                set_failed(r, std::string("symmetry gather launch failed: ") + gz_nn_last_error());
+                return;
+            }
+            segs = dsegs;
         }
         if (r->out_staging) {
             bool ok = hipEventRecord(b.evk, r->stream) == hipSuccess && hipStreamWaitEvent(r->out_stream, b.evk, 0) == hipSuccess;
@@ -706,6 +782,41 @@ extern "C" gz_runner* gz_runner_create(gz_net* net, const gz_sm* sm, const gz_tr
     return r;
 }
 
+// One symmetry per row from now on (include/gzero_nn.h).  Every refusal precedes the first device call.
+extern "C" int gz_runner_set_symmetry(gz_runner* r, gz_symmetry* s, unsigned salt) {
+    if (!r || !s) {
+        g_err = "runner: null argument";
+        return -1;
+    }
+    if (r->started) {
+        g_err = "runner: gz_runner_set_symmetry after gz_runner_start (set the symmetry before the runner starts)";
+        return -1;
+    }
+    if (r->zero_copy) {
+        g_err = "runner: gz_runner_set_symmetry on a zero-copy runner (GZ_RUNNER_ZERO_COPY=1): the pick reads the HBM plane staging";
+        return -1;
+    }
+    gzsym::NetView v;
+    if (gzsym::pick_check(r->net, s, &v) != 0) {
+        g_err = gz_nn_last_error();
+        return -1;
+    }
+    if (hipSetDevice(r->cfg.device) != hipSuccess || gzsym::pick_prepare(s, v) != 0) {
+        g_err = std::string("runner: symmetry tables: ") + gz_nn_last_error();
+        return -1;
+    }
+    if (!r->out_stream && hipStreamCreateWithFlags(&r->out_stream, hipStreamNonBlocking) != hipSuccess) {
+        g_err = "runner: stream creation failed";
+        return -1;
+    }
+    r->out_staging = true;           // the gather writes the slot's d_out; the third stream carries it
+    r->sym = s;
+    r->sym_salt = salt;
+    return 0;
+}
+
+extern "C" long gz_runner_sym_pick_rows(gz_runner* r) { return r ? r->sym_rows.load() : 0; }
+
 extern "C" int gz_runner_start(gz_runner* r) {
     // the pools' games are started by their engine threads; a second start would add a second
     // set of games with the same seeds
@@ -829,6 +940,9 @@ extern "C" void gz_runner_destroy(gz_runner* r) {
         if (b.evk) (void)hipEventDestroy(b.evk);
         if (b.d_planes) (void)hipFree(b.d_planes);
         if (b.d_out) (void)hipFree(b.d_out);
+        if (b.d_sym_planes) (void)hipFree(b.d_sym_planes);
+        if (b.d_picks) (void)hipFree(b.d_picks);
+        if (b.d_raw) (void)hipFree(b.d_raw);
     }
     if (r->stream) (void)hipStreamDestroy(r->stream);
     if (r->copy_stream) (void)hipStreamDestroy(r->copy_stream);

@@ -20,6 +20,10 @@
 //
 // The index arithmetic of both kernels and the table validation are plain / __host__ __device__
 // functions here, so that a CPU program can run them (tests/symmetry_host_check.cpp).
+//
+// Below the ensemble: one symmetry per row, picked from a hash of the row's own planes
+// (gz_net_forward_sym_pick, gz_runner_set_symmetry) -- the definition, likewise as functions a CPU
+// program runs (tests/symmetry_pick_host_check.cpp).
 #pragma once
 
 #include <cstddef>
@@ -85,6 +89,70 @@ inline int chunk_rows(int S, int env_rows) {
     return c < 1 ? 1 : c;
 }
 
+// ---- one symmetry per row, picked from the row's own planes (gz_net_forward_sym_pick) -------------
+// For a row of E plane elements with 32-bit patterns b_i as stored (-0.0 is not 0.0, a NaN is its
+// bits), S table elements and a 32-bit salt, all in wrapping uint32 arithmetic:
+//
+//   h = sum over i in [0, E) of fmix(b_i + 0x9E3779B9 * (i + 1))         pick_term, any order
+//   g = (uint64(fmix(h ^ salt)) * S) >> 32                                pick_element, in [0, S)
+//   X'[i] = X[plane_src[g][i]]                                            sym_pick_expand_kernel
+//   p', v' = the net's ordinary forward of X'
+//   out_r[m] = p'_r[move_src[g][r][m]],  values = v'                      sym_pick_gather_kernel
+//
+// The sum is modular, so every reduction tree gives the same h: the kernel's wave shuffles and the
+// loop below agree exactly.  No floating-point operation is added, so a picked row is bit for bit the
+// plain forward of the permuted planes read through the move table.  g is a function of the row's
+// planes, S and the salt alone: the same position gets the same element in any batch, slot or entry
+// point -- which a host RNG draw per leaf would not give.
+GZSYM_HD inline unsigned fmix32(unsigned x) {
+    x ^= x >> 16;
+    x *= 0x85ebca6bu;
+    x ^= x >> 13;
+    x *= 0xc2b2ae35u;
+    x ^= x >> 16;
+    return x;
+}
+
+// element i's term of the row hash
+GZSYM_HD inline unsigned pick_term(unsigned bits, unsigned i) { return fmix32(bits + 0x9E3779B9u * (i + 1u)); }
+
+GZSYM_HD inline int pick_element(unsigned h, unsigned salt, int S) {
+    return (int)(((unsigned long long)fmix32(h ^ salt) * (unsigned long long)S) >> 32);
+}
+
+// the row hash, serially (the CPU statement of what sym_pick_expand_kernel reduces in parallel)
+inline unsigned pick_hash(const unsigned* bits, int E) {
+    unsigned h = 0;
+    for (int i = 0; i < E; ++i) h += pick_term(bits[i], (unsigned)i);
+    return h;
+}
+
+// sym_pick_expand_kernel, element i of row r picked as g: where it reads in the planes [n][E]
+GZSYM_HD inline size_t pick_expand_src(int r, int i, int g, int E, const int* plane_src) {
+    return (size_t)r * (size_t)E + (size_t)plane_src[(size_t)g * E + i];
+}
+
+// sym_pick_gather_kernel, column m of row r of a role `width` wide: where it reads in the role's raw
+// outputs [n][width]; src is the role's move table [S][width], nullptr for the values
+GZSYM_HD inline size_t pick_gather_src(int r, int m, int g, int width, const int* src) {
+    return (size_t)r * (size_t)width + (size_t)(src ? src[(size_t)g * width + m] : m);
+}
+
+// Destinations of a gather launch: segment k holds rows [row0[k], row0[k + 1]) of the launch, written
+// to out[k][role] + (row - row0[k]) * width (role R: the values).  GZ_MAX_SEGMENTS segments at most.
+constexpr int kMaxPickSegments = 32;
+struct PickSegments {
+    int nseg;
+    int row0[kMaxPickSegments];
+    float* out[kMaxPickSegments][GZ_MAX_ROLES + 1];
+};
+
+GZSYM_HD inline int pick_find_segment(const PickSegments& sg, int row) {
+    int s = 0;
+    while (s + 1 < sg.nseg && row >= sg.row0[s + 1]) ++s;
+    return s;
+}
+
 // true when t[0 .. len) holds every value of 0 .. len - 1 once; else *bad = the first offending entry
 inline bool is_permutation(const int* t, int len, int* bad) {
     std::vector<char> seen((size_t)len, 0);
@@ -143,5 +211,19 @@ struct NetView {
 };
 void net_view(gz_net* net, NetView* out);
 int set_error(const std::string& msg);           // gz_nn_last_error's message; returns -1
+
+#if defined(__HIPCC__)
+// The pick path's pieces for a caller that owns its buffers and issues the net's forward itself (the
+// self-play runner; symmetry.hip defines them and uses them for its own entry points).
+// pick_check: the refusals of a pick forward, no device call.  pick_prepare: tables to the device
+// (once).  pick_expand_launch: rows [0, n) of d_in [n][E] hashed, picks[r] = g and x[r] = the row
+// permuted by element g (x == nullptr: the picks alone).  pick_gather_launch: raw[role] [n][P_r] and
+// raw[R] [n][V] read through move_src[picks[r]] into the segments' destinations.  One launch each.
+int pick_check(gz_net* net, gz_symmetry* s, NetView* v);
+int pick_prepare(gz_symmetry* s, const NetView& v);
+int pick_expand_launch(gz_symmetry* s, hipStream_t stream, unsigned salt, const float* d_in, int n, int* d_picks, float* d_x);
+int pick_gather_launch(gz_symmetry* s, hipStream_t stream, const int* d_picks, int n, const float* const* d_raw,
+                       const PickSegments& segs);
+#endif
 
 }  // namespace gzsym

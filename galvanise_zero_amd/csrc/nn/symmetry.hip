@@ -1,5 +1,6 @@
-// The symmetry ensemble's two kernels and entry points (symmetry.h states the arithmetic; the net's
-// own forward runs between the kernels, unchanged, through gz_net_forward_device).
+// The symmetry ensemble's two kernels and entry points, and below them the two kernels and entry
+// points of the one-symmetry-per-row pick (symmetry.h states the arithmetic of both; the net's own
+// forward runs between the kernels, unchanged, through gz_net_forward_device).
 #include "symmetry.h"
 
 #include <hip/hip_runtime.h>
@@ -27,7 +28,7 @@ struct gz_symmetry {
     const int* d_plane = nullptr;
     const int* d_move[GZ_MAX_ROLES] = {};
     float* d_scratch = nullptr;                  // expanded planes and raw outputs of one chunk
-    int scratch_rows = 0;                        // chunk rows the scratch holds
+    size_t scratch_floats = 0;                   // floats the scratch holds
     float* d_io = nullptr;                       // host entry point: a chunk's planes and results
     int io_rows = 0;
     std::mutex mu;                               // the host entry point: one call at a time
@@ -95,7 +96,7 @@ extern "C" void gz_symmetry_destroy(gz_symmetry* s) {
 extern "C" int gz_symmetry_count(const gz_symmetry* s) { return s ? s->L.S : 0; }
 
 // the refusals of a forward: nothing here touches the device
-static int check_net(gz_net* net, gz_symmetry* s, NetView* v) {
+static int check_net(gz_net* net, gz_symmetry* s, NetView* v, bool allow_logits = false) {
     net_view(net, v);
     bool same = v->plane_elems == s->E && v->roles == s->L.R;
     for (int r = 0; same && r < s->L.R; ++r) same = v->policy[r] == s->L.P[r];
@@ -112,7 +113,7 @@ static int check_net(gz_net* net, gz_symmetry* s, NetView* v) {
     if (s->L.total && v->num_values != s->L.V)
         return set_error("symmetry: tables in use with a net of " + std::to_string(s->L.V) + " values, this net has " +
                          std::to_string(v->num_values));
-    if (v->logits)
+    if (v->logits && !allow_logits)
         return set_error("symmetry: the net is in gz_net_set_output_logits mode (an average of logits is not the ensemble)");
     return 0;
 }
@@ -124,39 +125,49 @@ static int env_chunk_rows() {
     return e ? atoi(e) : 0;
 }
 
+// tables to the device (once)
+static int ensure_tables(gz_symmetry* s, const NetView& v) {
+    SYMCHK(hipSetDevice(s->device));
+    if (s->d_tables) return 0;
+    s->L.V = v.num_values;
+    s->L.total = v.num_values;
+    size_t ints = s->h_plane.size();
+    for (int r = 0; r < s->L.R; ++r) { ints += s->h_move[r].size(); s->L.total += s->L.P[r]; }
+    int* d = nullptr;
+    SYMCHK(hipMalloc((void**)&d, ints * sizeof(int)));
+    size_t off = 0;
+    hipError_t e = hipMemcpy(d, s->h_plane.data(), s->h_plane.size() * sizeof(int), hipMemcpyHostToDevice);
+    s->d_plane = d;
+    off += s->h_plane.size();
+    for (int r = 0; r < s->L.R && e == hipSuccess; ++r) {
+        e = hipMemcpy(d + off, s->h_move[r].data(), s->h_move[r].size() * sizeof(int), hipMemcpyHostToDevice);
+        s->d_move[r] = d + off;
+        off += s->h_move[r].size();
+    }
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return set_error(std::string("symmetry: table upload: ") + hipGetErrorString(e));
+    }
+    s->d_tables = d;
+    return 0;
+}
+
+// the object's scratch, grown to `floats` floats: sized for the mode in use (the ensemble's S x rows
+// expanded rows, or the pick path's rows with one int per row)
+static int ensure_scratch(gz_symmetry* s, size_t floats) {
+    if (floats <= s->scratch_floats) return 0;
+    if (s->d_scratch) SYMCHK(hipFree(s->d_scratch));   // (waits for the work queued on it)
+    s->d_scratch = nullptr;
+    s->scratch_floats = 0;
+    SYMCHK(hipMalloc((void**)&s->d_scratch, floats * sizeof(float)));
+    s->scratch_floats = floats;
+    return 0;
+}
+
 // tables to the device (once) and scratch for chunks of `rows` rows
 static int ensure_device(gz_symmetry* s, const NetView& v, int rows) {
-    SYMCHK(hipSetDevice(s->device));
-    if (!s->d_tables) {
-        s->L.V = v.num_values;
-        s->L.total = v.num_values;
-        size_t ints = s->h_plane.size();
-        for (int r = 0; r < s->L.R; ++r) { ints += s->h_move[r].size(); s->L.total += s->L.P[r]; }
-        int* d = nullptr;
-        SYMCHK(hipMalloc((void**)&d, ints * sizeof(int)));
-        size_t off = 0;
-        hipError_t e = hipMemcpy(d, s->h_plane.data(), s->h_plane.size() * sizeof(int), hipMemcpyHostToDevice);
-        s->d_plane = d;
-        off += s->h_plane.size();
-        for (int r = 0; r < s->L.R && e == hipSuccess; ++r) {
-            e = hipMemcpy(d + off, s->h_move[r].data(), s->h_move[r].size() * sizeof(int), hipMemcpyHostToDevice);
-            s->d_move[r] = d + off;
-            off += s->h_move[r].size();
-        }
-        if (e != hipSuccess) {
-            (void)hipFree(d);
-            return set_error(std::string("symmetry: table upload: ") + hipGetErrorString(e));
-        }
-        s->d_tables = d;
-    }
-    if (rows > s->scratch_rows) {
-        if (s->d_scratch) SYMCHK(hipFree(s->d_scratch));   // (waits for the work queued on it)
-        s->d_scratch = nullptr;
-        s->scratch_rows = 0;
-        SYMCHK(hipMalloc((void**)&s->d_scratch, (size_t)s->L.S * rows * row_floats(s) * sizeof(float)));
-        s->scratch_rows = rows;
-    }
-    return 0;
+    if (ensure_tables(s, v)) return -1;
+    return ensure_scratch(s, (size_t)s->L.S * rows * row_floats(s));
 }
 
 // rows [0, n) of d_planes through expand, the net's forward and reduce, chunk by chunk, on `stream`
@@ -239,5 +250,207 @@ extern "C" int gz_net_forward_sym(gz_net* net, gz_symmetry* s, const float* plan
                               stream));
     }
     SYMCHK(hipStreamSynchronize(stream));
+    return 0;
+}
+
+// ---- one symmetry per row, picked from the row's own planes (symmetry.h states the definition) ----
+
+struct GatherArgs {
+    OutLayout L;
+    int n;
+    const int* picks;                            // [n]
+    const float* raw[GZ_MAX_ROLES + 1];          // [n][P_r] per role; at index R the values [n][V]
+    const int* src[GZ_MAX_ROLES];                // [S][P_r]
+    PickSegments sg;
+};
+
+// One workgroup per row: the row's hash by wave shuffles and LDS (16-byte loads where E and the
+// row's address allow, a scalar loop otherwise and for the tail), g to picks[row], then the row
+// permuted through plane_src[g].  x == nullptr: the picks alone.
+__global__ void __launch_bounds__(256) sym_pick_expand_kernel(const float* __restrict__ in, float* __restrict__ x,
+                                                              int* __restrict__ picks, int n, int E, int S, unsigned salt,
+                                                              const int* __restrict__ plane_src) {
+    __shared__ unsigned part[4];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    if (row >= n) return;
+    const unsigned* b = (const unsigned*)in + (size_t)row * E;
+    unsigned h = 0;
+    int done = 0;
+    if (((uintptr_t)b & 15) == 0) {
+        const int n4 = E >> 2;
+        for (int i4 = tid; i4 < n4; i4 += 256) {
+            const uint4 v = ((const uint4*)b)[i4];
+            const unsigned i = 4u * (unsigned)i4;
+            h += pick_term(v.x, i) + pick_term(v.y, i + 1) + pick_term(v.z, i + 2) + pick_term(v.w, i + 3);
+        }
+        done = n4 << 2;
+    }
+    for (int i = done + tid; i < E; i += 256) h += pick_term(b[i], (unsigned)i);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) h += (unsigned)__shfl_xor((int)h, d, 64);
+    if ((tid & 63) == 0) part[tid >> 6] = h;
+    __syncthreads();
+    const int g = pick_element(part[0] + part[1] + part[2] + part[3], salt, S);
+    if (tid == 0) picks[row] = g;
+    if (!x) return;
+    for (int i = tid; i < E; i += 256) x[(size_t)row * E + i] = in[pick_expand_src(row, i, g, E, plane_src)];
+}
+
+// one thread per output element: blockIdx.y is the row, blockIdx.x covers its sum P_r + V columns
+__global__ void __launch_bounds__(256) sym_pick_gather_kernel(GatherArgs a) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    const int r = blockIdx.y;
+    if (j >= a.L.total || r >= a.n) return;
+    int role, m;
+    split_column(a.L, j, &role, &m);
+    const int width = role < a.L.R ? a.L.P[role] : a.L.V;
+    const int k = pick_find_segment(a.sg, r);
+    a.sg.out[k][role][(size_t)(r - a.sg.row0[k]) * width + m] =
+        a.raw[role][pick_gather_src(r, m, a.picks[r], width, role < a.L.R ? a.src[role] : nullptr)];
+}
+
+// the refusals of a pick forward: check_net's, except that a net in gz_net_set_output_logits mode is
+// served (a permutation of logits is the logits of the permuted position; nothing is averaged)
+int gzsym::pick_check(gz_net* net, gz_symmetry* s, NetView* v) { return check_net(net, s, v, true); }
+
+int gzsym::pick_prepare(gz_symmetry* s, const NetView& v) {
+    std::lock_guard<std::mutex> lk(s->mu);
+    return ensure_tables(s, v);
+}
+
+int gzsym::pick_expand_launch(gz_symmetry* s, hipStream_t stream, unsigned salt, const float* d_in, int n, int* d_picks,
+                              float* d_x) {
+    if (n <= 0) return 0;
+    sym_pick_expand_kernel<<<dim3((unsigned)n), dim3(256), 0, stream>>>(d_in, d_x, d_picks, n, s->E, s->L.S, salt, s->d_plane);
+    SYMCHK(hipGetLastError());
+    return 0;
+}
+
+int gzsym::pick_gather_launch(gz_symmetry* s, hipStream_t stream, const int* d_picks, int n, const float* const* d_raw,
+                              const PickSegments& segs) {
+    if (n <= 0) return 0;
+    if (segs.nseg < 1 || segs.nseg > kMaxPickSegments) return set_error("symmetry: pick gather of " + std::to_string(segs.nseg) + " segments");
+    GatherArgs a{};
+    a.L = s->L;
+    a.n = n;
+    a.picks = d_picks;
+    for (int r = 0; r <= s->L.R; ++r) a.raw[r] = d_raw[r];
+    for (int r = 0; r < s->L.R; ++r) a.src[r] = s->d_move[r];
+    a.sg = segs;
+    sym_pick_gather_kernel<<<dim3((unsigned)((s->L.total + 255) / 256), (unsigned)n), dim3(256), 0, stream>>>(a);
+    SYMCHK(hipGetLastError());
+    return 0;
+}
+
+// rows [0, n) of d_planes through pick + expand, the net's forward and the gather, chunk by chunk
+static int pick_chunks(gz_net* net, gz_symmetry* s, const NetView& v, unsigned salt, hipStream_t stream, const float* d_planes,
+                       int n, float* const* d_pol, float* d_val) {
+    const int E = s->E;
+    const int chunk = chunk_rows(1, env_chunk_rows());
+    if (ensure_tables(s, v)) return -1;
+    const int rows = std::min(n, chunk);
+    if (ensure_scratch(s, (size_t)rows * (row_floats(s) + 1))) return -1;   // + 1: the row's pick
+    for (int r0 = 0; r0 < n; r0 += chunk) {
+        const int c = std::min(chunk, n - r0);
+        float* x = s->d_scratch;
+        float* raw[GZ_MAX_ROLES + 1];
+        float* p = x + (size_t)c * E;
+        PickSegments sg{};
+        sg.nseg = 1;
+        sg.row0[0] = 0;
+        for (int r = 0; r < s->L.R; ++r) {
+            raw[r] = p;
+            sg.out[0][r] = d_pol[r] + (size_t)r0 * s->L.P[r];
+            p += (size_t)c * s->L.P[r];
+        }
+        raw[s->L.R] = p;
+        sg.out[0][s->L.R] = d_val + (size_t)r0 * s->L.V;
+        int* picks = (int*)(p + (size_t)c * s->L.V);
+        if (pick_expand_launch(s, stream, salt, d_planes + (size_t)r0 * E, c, picks, x)) return -1;
+        if (gz_net_forward_device(net, stream, x, c, raw, raw[s->L.R])) return -1;
+        if (pick_gather_launch(s, stream, picks, c, raw, sg)) return -1;
+    }
+    return 0;
+}
+
+extern "C" int gz_net_forward_sym_pick_device(gz_net* net, gz_symmetry* s, unsigned salt, void* stream, const float* d_planes,
+                                              int n, float* const* d_policies, float* d_values) {
+    if (!net || !s || !d_planes || !d_policies || !d_values) return set_error("symmetry: null argument");
+    NetView v;
+    if (pick_check(net, s, &v)) return -1;
+    if (n <= 0) return 0;
+    return pick_chunks(net, s, v, salt, (hipStream_t)stream, d_planes, n, d_policies, d_values);
+}
+
+// a chunk's planes and results of the host entry points
+static int ensure_io(gz_symmetry* s, int rows) {
+    if (rows <= s->io_rows) return 0;
+    if (s->d_io) SYMCHK(hipFree(s->d_io));
+    s->d_io = nullptr;
+    s->io_rows = 0;
+    SYMCHK(hipMalloc((void**)&s->d_io, (size_t)rows * row_floats(s) * sizeof(float)));
+    s->io_rows = rows;
+    return 0;
+}
+
+extern "C" int gz_net_forward_sym_pick(gz_net* net, gz_symmetry* s, unsigned salt, const float* planes, int n,
+                                       float* const* policies, float* values) {
+    if (!net || !s || !planes || !policies || !values) return set_error("symmetry: null argument");
+    NetView v;
+    if (pick_check(net, s, &v)) return -1;
+    if (n <= 0) return 0;
+    std::lock_guard<std::mutex> lk(s->mu);
+    hipStream_t stream = (hipStream_t)v.host_stream;
+    const int chunk = chunk_rows(1, env_chunk_rows());
+    if (ensure_tables(s, v) || ensure_io(s, std::min(n, chunk))) return -1;
+    const size_t E = (size_t)s->E;
+    for (int r0 = 0; r0 < n; r0 += chunk) {
+        const int c = std::min(chunk, n - r0);
+        float* d_in = s->d_io;
+        float* d_pol[GZ_MAX_ROLES];
+        float* p = d_in + (size_t)c * E;
+        for (int r = 0; r < s->L.R; ++r) { d_pol[r] = p; p += (size_t)c * s->L.P[r]; }
+        float* d_val = p;
+        SYMCHK(hipMemcpyAsync(d_in, planes + (size_t)r0 * E, (size_t)c * E * sizeof(float), hipMemcpyHostToDevice, stream));
+        if (pick_chunks(net, s, v, salt, stream, d_in, c, d_pol, d_val)) return -1;
+        for (int r = 0; r < s->L.R; ++r)
+            SYMCHK(hipMemcpyAsync(policies[r] + (size_t)r0 * s->L.P[r], d_pol[r], (size_t)c * s->L.P[r] * sizeof(float),
+                                  hipMemcpyDeviceToHost, stream));
+        SYMCHK(hipMemcpyAsync(values + (size_t)r0 * s->L.V, d_val, (size_t)c * s->L.V * sizeof(float), hipMemcpyDeviceToHost,
+                              stream));
+    }
+    SYMCHK(hipStreamSynchronize(stream));
+    return 0;
+}
+
+// The g of each row as sym_pick_expand_kernel computes it (no net: the hash needs the planes alone).
+// Synchronous, on the null stream, through buffers of its own.
+extern "C" int gz_symmetry_picks(gz_symmetry* s, unsigned salt, int device_ptr, const float* planes, int n, int* out) {
+    if (!s || !planes || !out) return set_error("symmetry: null argument");
+    if (n <= 0) return 0;
+    std::lock_guard<std::mutex> lk(s->mu);
+    SYMCHK(hipSetDevice(s->device));
+    const size_t E = (size_t)s->E;
+    const int chunk = std::min(n, chunk_rows(1, env_chunk_rows()));
+    char* mem = nullptr;
+    const size_t pick_bytes = ((size_t)chunk * sizeof(int) + 15) & ~(size_t)15;
+    SYMCHK(hipMalloc((void**)&mem, pick_bytes + (device_ptr ? 0 : (size_t)chunk * E * sizeof(float))));
+    int* d_picks = (int*)mem;
+    float* d_in = (float*)(mem + pick_bytes);
+    hipError_t e = hipSuccess;
+    for (int r0 = 0; r0 < n && e == hipSuccess; r0 += chunk) {
+        const int c = std::min(chunk, n - r0);
+        const float* src = planes + (size_t)r0 * E;
+        if (!device_ptr) {
+            e = hipMemcpy(d_in, src, (size_t)c * E * sizeof(float), hipMemcpyHostToDevice);
+            src = d_in;
+        }
+        if (e != hipSuccess) break;
+        sym_pick_expand_kernel<<<dim3((unsigned)c), dim3(256), 0, 0>>>(src, nullptr, d_picks, c, s->E, s->L.S, salt, nullptr);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpy(out + r0, d_picks, (size_t)c * sizeof(int), hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(mem);
+    if (e != hipSuccess) return set_error(std::string("symmetry: picks: ") + hipGetErrorString(e));
     return 0;
 }

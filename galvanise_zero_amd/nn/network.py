@@ -32,14 +32,22 @@ def desc_from_conf(nn_model_conf, generation_descr=None):
 class HipModel(object):
     """Model object with the Keras inference surface the hot path uses."""
 
-    def __init__(self, desc, weights, device=0, precision="bf16", shadow=None, symmetries=None):
+    def __init__(self, desc, weights, device=0, precision="bf16", shadow=None, symmetries=None,
+                 symmetry_mode="average", symmetry_salt=0):
         """shadow: None, or (precision, every, max_rows) -- HipNet.enable_shadow before the weights
         are set, e.g. ("fp32-ieee", 64, 256): the live check of this model's forwards against a
         second arithmetic mode (self.net.shadow_stats()).
         symmetries: None, or a util.symmetry.SymmetryTables (util.symmetry.tables_for_game):
         predict_on_batch then returns the forward averaged over those board symmetries
         (HipNet.forward(X, symmetry=...)), so a PlayPoller / PUCTPlayer / Supervisor handed this model
-        searches on the ensemble.  For match play and analysis: every evaluation costs S rows."""
+        searches on the ensemble.  For match play and analysis: every evaluation costs S rows.
+        symmetry_mode: "average" (that ensemble) or "pick": every row evaluated under ONE element,
+        hashed on the GPU from the row's own planes and symmetry_salt, its policies mapped back
+        (HipNet.forward(X, symmetry=..., pick=symmetry_salt)) -- one row per evaluation."""
+        if symmetry_mode not in ("average", "pick"):
+            raise ValueError('symmetry_mode %r: "average" or "pick"' % (symmetry_mode,))
+        if symmetry_mode == "pick" and symmetries is None:
+            raise ValueError('symmetry_mode "pick" needs symmetries=')
         self.desc = desc
         self.weights = weights
         self.net = HipNet(desc, device, precision)
@@ -47,12 +55,13 @@ class HipModel(object):
             self.net.enable_shadow(*shadow)
         self.net.set_weights(to_blob(weights))
         self.symmetry = self.net.make_symmetry(symmetries) if symmetries is not None else None
+        self.pick = (int(symmetry_salt) & 0xFFFFFFFF) if symmetry_mode == "pick" else None
 
     def predict_on_batch(self, X):
         X = np.asarray(X, dtype=np.float32)
         d = self.desc
         assert X.shape[1:] == (d.input_channels, d.input_columns, d.input_rows), X.shape
-        return self.net.forward(X, symmetry=self.symmetry)
+        return self.net.forward(X, symmetry=self.symmetry, pick=self.pick)
 
     def predict(self, X, batch_size=None):
         return self.predict_on_batch(X)

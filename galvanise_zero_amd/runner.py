@@ -12,7 +12,12 @@ from . import _native, cppinterface
 class SelfPlayRunner(object):
     def __init__(self, hip_net, sm, transformer, conf, device=0, num_threads=8, pools_per_thread=2,
                  batch_size=256, seed=0, game_index_base=0, keep_samples=False, max_launch_rows=0,
-                 spin_yield_playouts=0, min_launch_rows=0, max_launch_wait_us=0, per_pool_unique_states=True):
+                 spin_yield_playouts=0, min_launch_rows=0, max_launch_wait_us=0, per_pool_unique_states=True,
+                 symmetry=None, symmetry_salt=None):
+        """symmetry: None, or a _native.HipSymmetry (HipNet.make_symmetry): every leaf is evaluated
+        under one element of its tables, picked on the GPU from a hash of the row's own planes and
+        symmetry_salt (default: seed & 0xFFFFFFFF), and its policies mapped back
+        (gz_runner_set_symmetry, include/gzero_nn.h).  One forward per leaf, as without."""
         self.lib = _native.runner_lib()
         _native.engine_lib()
         self.net = hip_net
@@ -35,6 +40,21 @@ class SelfPlayRunner(object):
             raise RuntimeError("gz_runner_create: %s" % self.lib.gz_runner_last_error().decode())
         self.num_pools = num_threads * pools_per_thread
         self.batch_size = batch_size
+        self.symmetry = symmetry             # (kept alive: the runner reads its tables)
+        self.symmetry_salt = None
+        if symmetry is not None:
+            self.set_symmetry(symmetry, (seed if symmetry_salt is None else symmetry_salt) & 0xFFFFFFFF)
+
+    def set_symmetry(self, symmetry, salt):
+        """gz_runner_set_symmetry: before start() only."""
+        if self.lib.gz_runner_set_symmetry(self.handle, symmetry.handle, int(salt) & 0xFFFFFFFF) != 0:
+            raise RuntimeError("gz_runner_set_symmetry: %s" % self.lib.gz_runner_last_error().decode())
+        self.symmetry = symmetry
+        self.symmetry_salt = int(salt) & 0xFFFFFFFF
+
+    def sym_pick_rows(self):
+        """Rows that went through the one-symmetry-per-row path (gz_runner_sym_pick_rows)."""
+        return int(self.lib.gz_runner_sym_pick_rows(self.handle))
 
     def start(self):
         if self.lib.gz_runner_start(self.handle) != 0:

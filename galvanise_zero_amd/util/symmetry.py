@@ -112,6 +112,46 @@ def _name_perm(names, applies, skips, x_cords, y_cords, element, what):
     return perm
 
 
+def _fmix32(x):
+    x = x ^ (x >> np.uint32(16))
+    x = x * np.uint32(0x85ebca6b)
+    x = x ^ (x >> np.uint32(13))
+    x = x * np.uint32(0xc2b2ae35)
+    return x ^ (x >> np.uint32(16))
+
+
+def pick_hashes(X):
+    """The row hash h of csrc/nn/symmetry.h for every row of X (float32 [n, ...], read as the 32-bit
+    patterns stored: -0.0 is not 0.0): sum over i of fmix(b_i + 0x9E3779B9 * (i + 1)) mod 2^32."""
+    X = np.ascontiguousarray(X, dtype=np.float32)
+    bits = X.reshape(X.shape[0], -1).view(np.uint32)
+    with np.errstate(over="ignore"):
+        k = np.uint32(0x9E3779B9) * np.arange(1, bits.shape[1] + 1, dtype=np.uint32)
+        return _fmix32(bits + k[None, :]).sum(axis=1, dtype=np.uint32)
+
+
+def pick_elements(X, S, salt):
+    """The table element g in [0, S) under which gz_net_forward_sym_pick evaluates each row of X:
+    g = (uint64(fmix(h ^ salt)) * S) >> 32, the numpy statement of the GPU kernel's hash (the reference
+    for tests and for oracle-side model wrappers).  Returns int32 [n]."""
+    with np.errstate(over="ignore"):
+        f = _fmix32(pick_hashes(X) ^ np.uint32(int(salt) & 0xFFFFFFFF))
+    return ((f.astype(np.uint64) * np.uint64(S)) >> np.uint64(32)).astype(np.int32)
+
+
+def pick_forward(forward, X, tables, salt):
+    """The pick forward from a plain one, in numpy: `forward(X) -> [policy_0 .. policy_{R-1}, values]`
+    applied to each row permuted by its element, the policies read back through move_src.  What
+    gz_net_forward_sym_pick computes, for oracle-side wrappers and tests."""
+    X = np.ascontiguousarray(X, dtype=np.float32)
+    n = X.shape[0]
+    plane_src, move_src = np.asarray(tables.plane_src), [np.asarray(m) for m in tables.move_src]
+    g = pick_elements(X, plane_src.shape[0], salt)
+    flat = X.reshape(n, -1)
+    outs = forward(np.ascontiguousarray(np.take_along_axis(flat, plane_src[g], axis=1)).reshape(X.shape))
+    return [np.ascontiguousarray(np.take_along_axis(o, move_src[r][g], axis=1)) for r, o in enumerate(outs[:-1])] + [outs[-1]]
+
+
 def check_permutation(table, what):
     t = np.asarray(table)
     if t.ndim != 1 or not np.array_equal(np.sort(t), np.arange(len(t))):

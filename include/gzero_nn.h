@@ -320,6 +320,34 @@ int gz_net_forward_sym(gz_net* net, gz_symmetry* s, const float* planes, int n, 
 int gz_net_forward_sym_device(gz_net* net, gz_symmetry* s, void* stream, const float* d_planes, int n,
                               float* const* d_policies, float* d_values);
 
+/* ---- one symmetry per row, picked from the row's own planes ---------------------------------------
+ * The one-evaluation form (AlphaGo Zero's self-play, KataGo's nnRandomize): each row is evaluated
+ * under ONE element g of the tables and its policy mapped back -- one forward, not S.  g is not drawn
+ * from a host RNG but hashed on the GPU from the row's own planes, so a row's result stays a function
+ * of that row alone (any batch, slot, pool, entry point or replay gives the same bits).  With b_i the
+ * 32-bit pattern of plane element i as stored (-0.0 differs from 0.0), E = plane_elems, S = count and
+ * a 32-bit salt, in wrapping uint32 arithmetic:
+ *   fmix(x): x ^= x>>16; x *= 0x85ebca6b; x ^= x>>13; x *= 0xc2b2ae35; x ^= x>>16
+ *   h = sum over i in [0, E) of fmix(b_i + 0x9E3779B9 * (i + 1))
+ *   g = (uint64(fmix(h ^ salt)) * S) >> 32                                  in [0, S)
+ *   X'[i] = X[plane_src[g][i]];  p', v' = the net's ordinary forward of X';
+ *   out_r[m] = p'_r[move_src[r][g][m]];  values = v'
+ * No floating-point operation is added: a picked row is bit for bit the plain forward of the permuted
+ * planes read through the move table, and count = 1 is gz_net_forward.  Two kernels
+ * (csrc/nn/symmetry.hip: sym_pick_expand_kernel hashes and permutes, sym_pick_gather_kernel maps back)
+ * around one gz_net_forward_device per chunk of 2,048 rows (GZ_SYM_CHUNK_ROWS lowers it), through the
+ * gz_symmetry's scratch.  Refusals ("symmetry: ...", before any device call): tables that are not the
+ * net's or were made for another device.  A net in gz_net_set_output_logits mode IS served: a
+ * permutation of logits is the logits of the permuted position (nothing is averaged).
+ * Whether this plays or trains stronger is the literature's claim; it is not measured here. */
+int gz_net_forward_sym_pick(gz_net* net, gz_symmetry* s, unsigned salt, const float* planes, int n,
+                            float* const* policies, float* values);
+int gz_net_forward_sym_pick_device(gz_net* net, gz_symmetry* s, unsigned salt, void* stream, const float* d_planes, int n,
+                                   float* const* d_policies, float* d_values);
+/* The g of each row of planes [n][plane_elems] (host memory, or device memory when device_ptr), as
+ * the GPU kernel computes it: for tests and diagnostics.  Synchronous. */
+int gz_symmetry_picks(gz_symmetry* s, unsigned salt, int device_ptr, const float* planes, int n, int* out);
+
 /* Diagnostics: with GZ_KERNEL_STAMPS set in the environment, gz_net_forward records per-workgroup
  * s_memtime stamps at phase boundaries; out8[0] = workgroups averaged, out8[1..4] = their mean
  * cycles of (input + initial conv, residual trunk, head 1x1 convs + features, fused dense heads)
@@ -382,6 +410,19 @@ typedef struct gz_runner_stats {
 gz_runner* gz_runner_create(gz_net* net, const struct gz_sm* sm, const struct gz_transformer* t,
                             const gz_runner_config* cfg, const struct gz_selfplay_config* conf,
                             const int* policy_sizes, int num_policies, int num_values);
+/* Self-play under one board symmetry per position (gz_net_forward_sym_pick's definition, above): every
+ * row of every launch is hashed, permuted, evaluated and mapped back on the GPU.  The launcher stages
+ * the planes in HBM as always, sym_pick_expand_kernel writes the permuted rows to a second per-slot
+ * buffer the forward reads, the forward writes raw outputs to a per-slot buffer and
+ * sym_pick_gather_kernel writes the slot's output staging, which the third stream copies to the
+ * pools' pinned buffers (output staging is forced on) -- one launch of each kernel per net launch.
+ * Before gz_runner_start only.  Refused ("runner: ..." / "symmetry: ..."), before any device call: a
+ * started runner; a zero-copy runner (GZ_RUNNER_ZERO_COPY=1: the pick needs the HBM plane staging);
+ * tables that are not the net's or were made for another device.  The gz_symmetry must outlive the
+ * runner.  Without this call the launcher issues exactly the calls it always did. */
+int gz_runner_set_symmetry(gz_runner* r, gz_symmetry* s, unsigned salt);
+/* rows that went through the pick path (equal to gz_runner_stats.rows with a symmetry set, else 0) */
+long gz_runner_sym_pick_rows(gz_runner* r);
 int gz_runner_start(gz_runner* r);   /* once per runner: a stopped runner cannot be restarted */
 int gz_runner_wait_batches(gz_runner* r, long total_batches, double timeout_s);
 int gz_runner_wait_rows(gz_runner* r, long total_rows, double timeout_s);
