@@ -209,8 +209,64 @@ def nn_lib():
                                                            ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
                                                            ctypes.c_void_p]
             lib.gz_symmetry_picks.argtypes = [ctypes.c_void_p, ctypes.c_uint, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, _IP]
+        if hasattr(lib, "gz_eval_cache_create"):   # (absent from older A/B builds loaded through GZ_LIB_DIR)
+            lib.gz_eval_cache_create.restype = ctypes.c_void_p
+            lib.gz_eval_cache_create.argtypes = [ctypes.c_void_p, ctypes.c_long]
+            lib.gz_eval_cache_destroy.argtypes = [ctypes.c_void_p]
+            lib.gz_eval_cache_clear.argtypes = [ctypes.c_void_p]
+            lib.gz_eval_cache_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(GzEvalCacheStats), ctypes.c_int]
+            lib.gz_net_forward_cached.argtypes = [ctypes.c_void_p, ctypes.c_void_p, _FP, ctypes.c_int, ctypes.POINTER(_FP), _FP]
+            lib.gz_net_forward_cached_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                         ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]
+            lib.gz_eval_cache_probe.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, _IP]
         lib._gz_typed = True
     return lib
+
+
+class GzEvalCacheStats(ctypes.Structure):
+    """struct gz_eval_cache_stats (include/gzero_nn.h)."""
+    _fields_ = [(n, ctypes.c_long) for n in ("calls", "rows", "hits", "forward_rows", "inserts", "replaced", "flushes",
+                                             "entries", "entry_bytes")]
+
+
+class HipEvalCache(object):
+    """Owner of a gz_eval_cache handle (include/gzero_nn.h): a direct-mapped table of `entries`
+    evaluated rows in HBM for one HipNet, keyed by a row's planes and exact -- a hit returns the bits
+    the forward would write.  Pass it to HipNet.forward(X, cache=...); util.evalcache.CacheModel says
+    which rows hit.  Weight rolls and set_output_logits flush it; clear() does so by hand."""
+
+    def __init__(self, net, entries):
+        self.lib = nn_lib()
+        if not hasattr(self.lib, "gz_eval_cache_create"):
+            raise RuntimeError("libgz_nn.so has no evaluation cache (an older build)")
+        self.net = net
+        self.entries = int(entries)
+        self.handle = self.lib.gz_eval_cache_create(net.handle if net is not None else None, self.entries)
+        if not self.handle:
+            raise RuntimeError("gz_eval_cache_create failed: %s" % self.lib.gz_nn_last_error().decode())
+
+    def stats(self, reset=False):
+        """gz_eval_cache_stats as a dict: calls, rows, hits, forward_rows, inserts, replaced, flushes,
+        entries, entry_bytes.  Waits for the cache's last call on the device."""
+        st = GzEvalCacheStats()
+        if self.lib.gz_eval_cache_stats(self.handle, ctypes.byref(st), int(bool(reset))) != 0:
+            raise RuntimeError("gz_eval_cache_stats failed: %s" % self.lib.gz_nn_last_error().decode())
+        return {n: getattr(st, n) for n, _ in st._fields_}
+
+    def clear(self):
+        if self.lib.gz_eval_cache_clear(self.handle) != 0:
+            raise RuntimeError("gz_eval_cache_clear failed: %s" % self.lib.gz_nn_last_error().decode())
+
+    def close(self):
+        if self.handle:
+            self.lib.gz_eval_cache_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class HipSymmetry(object):
@@ -362,12 +418,21 @@ class HipNet(object):
         forward(X, symmetry=...); that the tables fit this net is checked by the forward."""
         return HipSymmetry(tables.plane_src, tables.move_src, self.device)
 
-    def forward(self, planes, symmetry=None, pick=None):
-        """symmetry: None, or a HipSymmetry (make_symmetry): the forward averaged over its board
+    def make_cache(self, entries):
+        """A HipEvalCache of `entries` entries for this net (gz_eval_cache_create)."""
+        return HipEvalCache(self, entries)
+
+    def forward(self, planes, symmetry=None, pick=None, cache=None):
+        """cache: None, or a HipEvalCache (make_cache): rows evaluated before are answered from the
+        table, the others go through the forward and are stored (gz_net_forward_cached) -- the same
+        bits either way.  Not together with symmetry=.
+        symmetry: None, or a HipSymmetry (make_symmetry): the forward averaged over its board
         symmetries (gz_net_forward_sym, include/gzero_nn.h).  pick: None for that ensemble, or a
         32-bit salt: each row evaluated under ONE element of the tables, hashed on the GPU from the
         row's own planes and the salt, its policies mapped back (gz_net_forward_sym_pick) -- one
         forward, bit for bit the plain forward of the permuted row read through the move table."""
+        if cache is not None and symmetry is not None:
+            raise ValueError("cache= together with symmetry=: the two do not compose")
         d = self.desc
         planes = np.ascontiguousarray(planes, dtype=np.float32)
         n = planes.shape[0]
@@ -375,6 +440,10 @@ class HipNet(object):
         pols = [np.empty((n, p), dtype=np.float32) for p in d.policy_dist_count]
         val = np.empty((n, d.num_values), dtype=np.float32)
         arr = (_FP * len(pols))(*[_fptr(p) for p in pols])
+        if cache is not None:
+            self._check(self.lib.gz_net_forward_cached(self.handle, cache.handle, _fptr(planes), n, arr, _fptr(val)),
+                        "gz_net_forward_cached")
+            return pols + [val]
         if pick is not None:
             if symmetry is None:
                 raise ValueError("pick=%r needs symmetry=" % (pick,))
@@ -395,6 +464,27 @@ class HipNet(object):
                                                    ctypes.c_void_p(d_planes), n, arr,
                                                    ctypes.c_void_p(d_values)),
                     "gz_net_forward_device")
+
+    def forward_cached_device(self, cache, stream, d_planes, n, d_policies, d_values):
+        """gz_net_forward_cached_device: the cached forward on `stream`, device pointers as
+        forward_device; outputs complete in stream order.  Blocks once per chunk of 2,048 rows."""
+        arr = (ctypes.c_void_p * len(d_policies))(*d_policies)
+        self._check(self.lib.gz_net_forward_cached_device(self.handle, cache.handle, ctypes.c_void_p(stream),
+                                                          ctypes.c_void_p(d_planes), n, arr, ctypes.c_void_p(d_values)),
+                    "gz_net_forward_cached_device")
+
+    def cache_probe(self, cache, planes=None, device_ptr=None, n=None):
+        """The hit mask of rows against `cache` as it stands, without side effects (gz_eval_cache_probe):
+        planes a host array [n, ...], or device_ptr + n.  int32 [n]."""
+        if planes is not None:
+            planes = np.ascontiguousarray(planes, dtype=np.float32)
+            n, ptr, dev = planes.shape[0], planes.ctypes.data, 0
+        else:
+            ptr, dev = device_ptr, 1
+        out = np.zeros(n, dtype=np.int32)
+        self._check(self.lib.gz_eval_cache_probe(cache.handle, dev, ctypes.c_void_p(ptr), n, out.ctypes.data_as(_IP)),
+                    "gz_eval_cache_probe")
+        return out
 
     def forward_sym_device(self, symmetry, stream, d_planes, n, d_policies, d_values):
         """gz_net_forward_sym_device: the symmetry ensemble on `stream`, device pointers as forward_device.
@@ -789,6 +879,8 @@ def runner_lib():
         lib.gz_runner_roll_info.argtypes = [_VP, ctypes.POINTER(ctypes.c_long), ctypes.c_int,
                                             ctypes.POINTER(ctypes.c_long)]
         lib.gz_runner_ordinal_stats.argtypes = [_VP, ctypes.POINTER(GzOrdinalStats)]
+        if hasattr(lib, "gz_runner_set_cache"):   # (absent from older A/B builds loaded through GZ_LIB_DIR)
+            lib.gz_runner_set_cache.argtypes = [_VP, _VP]
         if hasattr(lib, "gz_runner_set_symmetry"):   # (absent from older A/B builds loaded through GZ_LIB_DIR)
             lib.gz_runner_set_symmetry.argtypes = [_VP, _VP, ctypes.c_uint]
             lib.gz_runner_sym_pick_rows.restype = ctypes.c_long

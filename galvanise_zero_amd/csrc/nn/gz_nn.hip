@@ -8,6 +8,7 @@
 #include "trunk_variants.h"
 #include "fp32_forward.h"
 #include "layered_forward.h"
+#include "eval_cache.h"
 #include "shadow_compare.h"
 #include "symmetry.h"
 #include "weight_image.h"
@@ -66,6 +67,8 @@ struct gz_net : PackSpec {         // d, fpad, p2, K0, cp, fp32, gemm_heads: wha
     char* dmem = nullptr;          // all weights, one allocation
     KParams kp{};                  // weight pointers filled in, outputs per launch
     std::mutex wmu;                // guards dmem / kp's weight pointers / has_weights (weight rolls)
+    unsigned long long wepoch = 1; // weight generation (under wmu): every installed image and every change of
+                                   // kp.logits bumps it; an evaluation cache flushes when it moves (eval_cache.h)
 
     hipStream_t stream = nullptr;  // for the synchronous host-buffer forward
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -685,6 +688,7 @@ char* swap_image(gz_net* net, char* m, const ImageLayout& I) {
 int install_image(gz_net* net, char* m, const ImageLayout& I, char* sm = nullptr, const ImageLayout* sI = nullptr) {
     std::unique_lock<std::mutex> wl(net->wmu);
     char* old = swap_image(net, m, I);
+    ++net->wepoch;
     char* sold = nullptr;
     if (sm && net->shadow) {
         sold = swap_image(net->shadow->net, sm, *sI);
@@ -1077,10 +1081,11 @@ static int shadow_check(gz_net* net, hipStream_t stream, const gz_segment* segs,
 
 // `end` (may be NULL) is recorded after the net's own launches, before a shadow check's.
 static int launch_segments(gz_net* net, hipStream_t stream, const gz_segment* segs, int nseg,
-                           hipEvent_t mid = nullptr, hipEvent_t end = nullptr) {
+                           hipEvent_t mid = nullptr, hipEvent_t end = nullptr, unsigned long long* epoch = nullptr) {
     // the weight image stays valid until this launch is queued (gz_net_set_weights frees a replaced
     // image only after a device sync)
     std::lock_guard<std::mutex> wl(net->wmu);
+    if (epoch) *epoch = net->wepoch;
     int n = 0;
     if (launch_net(net, stream, segs, nseg, mid, &n)) return -1;
     if (end) HIPCHK(hipEventRecord(end, stream));
@@ -1183,6 +1188,7 @@ extern "C" float gz_net_last_kernel_ms(const gz_net* net) { return net ? net->la
 extern "C" int gz_net_set_output_logits(gz_net* net, int on) {
     if (!net) return fail("null net");
     std::lock_guard<std::mutex> wl(net->wmu);
+    if (net->kp.logits != (on ? 1 : 0)) ++net->wepoch;   // stored outputs are what the forward wrote
     net->kp.logits = on ? 1 : 0;
     if (net->shadow) net->shadow->net->kp.logits = net->kp.logits;
     return 0;
@@ -1202,6 +1208,16 @@ void gzsym::net_view(gz_net* net, gzsym::NetView* out) {
 }
 
 int gzsym::set_error(const std::string& msg) { return fail(msg); }
+
+// what eval_cache.hip (the evaluation cache) needs beyond that
+unsigned long long gzcache::net_epoch(gz_net* net) {
+    std::lock_guard<std::mutex> wl(net->wmu);
+    return net->wepoch;
+}
+
+int gzcache::forward_segments_epoch(gz_net* net, void* stream, const gz_segment* segs, int nseg, unsigned long long* epoch) {
+    return launch_segments(net, (hipStream_t)stream, segs, nseg, nullptr, nullptr, epoch);
+}
 
 extern "C" int gz_nn_compare_outputs(int device, int n, int roles, const int* policy_sizes, int num_values,
                                      const float* const* pol_a, const float* val_a, const float* const* pol_b,

@@ -14,6 +14,7 @@
 // planes itself (no staging copy; round 1).
 #include "../../../include/gzero_engine.h"
 #include "../../../include/gzero_nn.h"
+#include "eval_cache.h"
 #include "symmetry.h"
 
 #include <hip/hip_runtime.h>
@@ -120,6 +121,9 @@ struct gz_runner {
     gz_symmetry* sym = nullptr;
     unsigned sym_salt = 0;
     std::atomic<long> sym_rows{0};   // rows that went through the pick path
+    // gz_runner_set_cache: every launch goes through the evaluation cache (csrc/nn/eval_cache.h): the
+    // rows that hit are answered from the table, the others alone go through the forward; null: none
+    gz_eval_cache* cache = nullptr;
     Compose compose = kSplit;
     Batch batches_ring[2];
 
@@ -301,15 +305,15 @@ static void launcher_main(gz_runner* r) {
     int next_slot = 0;
     long launches_issued = 0;
     std::vector<gz_segment> segs, hsegs, dsegs;
-    while (true) {
-        // retire finished batches (in order: one stream)
+    // retire finished batches (in order: one stream); false: a launch failed
+    auto retire = [&]() -> bool {
         while (!inflight.empty()) {
             Batch& b = r->batches_ring[inflight.front()];
             const hipError_t q = hipEventQuery(b.ev1);
             if (q == hipErrorNotReady) break;
             if (q != hipSuccess) {
                 set_failed(r, std::string("forward failed: ") + hipGetErrorString(q));
-                return;
+                return false;
             }
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, b.ev0, r->out_staging ? b.evk : b.ev1) == hipSuccess)
@@ -341,6 +345,21 @@ static void launcher_main(gz_runner* r) {
             inflight.pop_front();
             r->cv.notify_all();
         }
+        return true;
+    };
+    // a cached launch waits for its count of misses: the older launch retires meanwhile, so that the
+    // wait does not hold back its pools
+    struct Idle {
+        decltype(retire)* retire;
+        bool ok;
+    } idle_ctx{&retire, true};
+    auto idle = [](void* p) {
+        Idle* c = (Idle*)p;
+        if (c->ok) c->ok = (*c->retire)();
+        std::this_thread::yield();
+    };
+    while (true) {
+        if (!retire()) return;
         if (r->stop.load(std::memory_order_relaxed)) {
             if (inflight.empty()) return;
             std::this_thread::sleep_for(std::chrono::microseconds(50));
@@ -617,8 +636,29 @@ static void launcher_main(gz_runner* r) {
                 row += sg.rows;
             }
         }
-        if (hipEventRecord(b.ev0, r->stream) != hipSuccess ||
-            gz_net_forward_segments_ev(r->net, r->stream, segs.data(), (int)segs.size(), b.evm) != 0) {
+        if (r->cache) {
+            // probe + compact, the count of misses, the forward of the misses alone, fill: the rows'
+            // destinations are the segments' (the pools' pinned buffers, or the d_out blocks); an
+            // all-hit launch records its events without a forward (evm at the end: there is no trunk
+            // launch to time apart)
+            gzsym::PickSegments ps{};
+            ps.nseg = (int)segs.size();
+            int row = 0;
+            for (size_t k = 0; k < segs.size(); ++k) {
+                ps.row0[k] = row;
+                row += segs[k].rows;
+                for (int j = 0; j < r->num_policies; ++j) ps.out[k][j] = segs[k].policies[j];
+                ps.out[k][r->num_policies] = segs[k].values;
+            }
+            if (hipEventRecord(b.ev0, r->stream) != hipSuccess ||
+                gzcache::cached_launch(r->net, r->cache, r->stream, b.d_planes, b.rows, ps, idle, &idle_ctx) != 0 ||
+                hipEventRecord(b.evm, r->stream) != hipSuccess) {
+                set_failed(r, std::string("cached launch failed: ") + gz_nn_last_error());
+                return;
+            }
+            if (!idle_ctx.ok) return;
+        } else if (hipEventRecord(b.ev0, r->stream) != hipSuccess ||
+                   gz_net_forward_segments_ev(r->net, r->stream, segs.data(), (int)segs.size(), b.evm) != 0) {
             set_failed(r, std::string("launch failed: ") + gz_nn_last_error());
             return;
         }
@@ -796,6 +836,10 @@ extern "C" int gz_runner_set_symmetry(gz_runner* r, gz_symmetry* s, unsigned sal
         g_err = "runner: gz_runner_set_symmetry on a zero-copy runner (GZ_RUNNER_ZERO_COPY=1): the pick reads the HBM plane staging";
         return -1;
     }
+    if (r->cache) {
+        g_err = "runner: gz_runner_set_symmetry on a runner with an evaluation cache (the two do not compose)";
+        return -1;
+    }
     gzsym::NetView v;
     if (gzsym::pick_check(r->net, s, &v) != 0) {
         g_err = gz_nn_last_error();
@@ -816,6 +860,33 @@ extern "C" int gz_runner_set_symmetry(gz_runner* r, gz_symmetry* s, unsigned sal
 }
 
 extern "C" long gz_runner_sym_pick_rows(gz_runner* r) { return r ? r->sym_rows.load() : 0; }
+
+// Every launch through the evaluation cache from now on (include/gzero_nn.h).  Every refusal precedes
+// the first device call.
+extern "C" int gz_runner_set_cache(gz_runner* r, gz_eval_cache* c) {
+    if (!r || !c) {
+        g_err = "runner: null argument";
+        return -1;
+    }
+    if (r->started) {
+        g_err = "runner: gz_runner_set_cache after gz_runner_start (set the cache before the runner starts)";
+        return -1;
+    }
+    if (r->zero_copy) {
+        g_err = "runner: gz_runner_set_cache on a zero-copy runner (GZ_RUNNER_ZERO_COPY=1): the probe reads the HBM plane staging";
+        return -1;
+    }
+    if (r->sym) {
+        g_err = "runner: gz_runner_set_cache on a runner with a symmetry (the two do not compose)";
+        return -1;
+    }
+    if (gzcache::runner_check(r->net, c) != 0) {
+        g_err = gz_nn_last_error();
+        return -1;
+    }
+    r->cache = c;
+    return 0;
+}
 
 extern "C" int gz_runner_start(gz_runner* r) {
     // the pools' games are started by their engine threads; a second start would add a second

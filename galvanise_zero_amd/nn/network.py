@@ -33,7 +33,7 @@ class HipModel(object):
     """Model object with the Keras inference surface the hot path uses."""
 
     def __init__(self, desc, weights, device=0, precision="bf16", shadow=None, symmetries=None,
-                 symmetry_mode="average", symmetry_salt=0):
+                 symmetry_mode="average", symmetry_salt=0, cache_entries=None):
         """shadow: None, or (precision, every, max_rows) -- HipNet.enable_shadow before the weights
         are set, e.g. ("fp32-ieee", 64, 256): the live check of this model's forwards against a
         second arithmetic mode (self.net.shadow_stats()).
@@ -43,7 +43,12 @@ class HipModel(object):
         searches on the ensemble.  For match play and analysis: every evaluation costs S rows.
         symmetry_mode: "average" (that ensemble) or "pick": every row evaluated under ONE element,
         hashed on the GPU from the row's own planes and symmetry_salt, its policies mapped back
-        (HipNet.forward(X, symmetry=..., pick=symmetry_salt)) -- one row per evaluation."""
+        (HipNet.forward(X, symmetry=..., pick=symmetry_salt)) -- one row per evaluation.
+        cache_entries: None, or the entries of an evaluation cache (HipNet.make_cache): predict_on_batch
+        answers rows evaluated before from the table, bit for bit what the forward gives
+        (self.cache.stats()).  Not together with symmetries=."""
+        if cache_entries is not None and symmetries is not None:
+            raise ValueError("cache_entries= together with symmetries=: the two do not compose")
         if symmetry_mode not in ("average", "pick"):
             raise ValueError('symmetry_mode %r: "average" or "pick"' % (symmetry_mode,))
         if symmetry_mode == "pick" and symmetries is None:
@@ -56,11 +61,14 @@ class HipModel(object):
         self.net.set_weights(to_blob(weights))
         self.symmetry = self.net.make_symmetry(symmetries) if symmetries is not None else None
         self.pick = (int(symmetry_salt) & 0xFFFFFFFF) if symmetry_mode == "pick" else None
+        self.cache = self.net.make_cache(cache_entries) if cache_entries is not None else None
 
     def predict_on_batch(self, X):
         X = np.asarray(X, dtype=np.float32)
         d = self.desc
         assert X.shape[1:] == (d.input_channels, d.input_columns, d.input_rows), X.shape
+        if self.cache is not None:
+            return self.net.forward(X, cache=self.cache)
         return self.net.forward(X, symmetry=self.symmetry, pick=self.pick)
 
     def predict(self, X, batch_size=None):

@@ -13,8 +13,12 @@ class SelfPlayRunner(object):
     def __init__(self, hip_net, sm, transformer, conf, device=0, num_threads=8, pools_per_thread=2,
                  batch_size=256, seed=0, game_index_base=0, keep_samples=False, max_launch_rows=0,
                  spin_yield_playouts=0, min_launch_rows=0, max_launch_wait_us=0, per_pool_unique_states=True,
-                 symmetry=None, symmetry_salt=None):
-        """symmetry: None, or a _native.HipSymmetry (HipNet.make_symmetry): every leaf is evaluated
+                 symmetry=None, symmetry_salt=None, cache=None):
+        """cache: None, or a _native.HipEvalCache of hip_net (HipNet.make_cache): every launch goes
+        through it -- rows evaluated before are answered from the table, the others alone go through
+        the forward (gz_runner_set_cache, include/gzero_nn.h); the samples are bit for bit those of a
+        runner without one.  Not together with symmetry=.
+        symmetry: None, or a _native.HipSymmetry (HipNet.make_symmetry): every leaf is evaluated
         under one element of its tables, picked on the GPU from a hash of the row's own planes and
         symmetry_salt (default: seed & 0xFFFFFFFF), and its policies mapped back
         (gz_runner_set_symmetry, include/gzero_nn.h).  One forward per leaf, as without."""
@@ -44,6 +48,21 @@ class SelfPlayRunner(object):
         self.symmetry_salt = None
         if symmetry is not None:
             self.set_symmetry(symmetry, (seed if symmetry_salt is None else symmetry_salt) & 0xFFFFFFFF)
+        self.cache = None
+        if cache is not None:
+            self.set_cache(cache)
+
+    def set_cache(self, cache):
+        """gz_runner_set_cache: before start() only."""
+        if not hasattr(self.lib, "gz_runner_set_cache"):
+            raise RuntimeError("libgz_nn.so has no evaluation cache (an older build)")
+        if self.lib.gz_runner_set_cache(self.handle, cache.handle) != 0:
+            raise RuntimeError("gz_runner_set_cache: %s" % self.lib.gz_runner_last_error().decode())
+        self.cache = cache                   # (kept alive: the launcher calls it)
+
+    def cache_stats(self, reset=False):
+        """The cache's gz_eval_cache_stats as a dict (None without a cache); safe while the runner runs."""
+        return self.cache.stats(reset) if self.cache is not None else None
 
     def set_symmetry(self, symmetry, salt):
         """gz_runner_set_symmetry: before start() only."""

@@ -348,6 +348,59 @@ int gz_net_forward_sym_pick_device(gz_net* net, gz_symmetry* s, unsigned salt, v
  * the GPU kernel computes it: for tests and diagnostics.  Synchronous. */
 int gz_symmetry_picks(gz_symmetry* s, unsigned salt, int device_ptr, const float* planes, int n, int* out);
 
+/* ---- evaluation cache: stored outputs for rows evaluated before ------------------------------------
+ * Every forward mode computes a row's outputs from that row alone, so a table that returns the stored
+ * outputs of a row returns the very bits the forward would write: the cache is exact.  A gz_eval_cache
+ * is a direct-mapped table of `entries` entries in HBM, keyed by the row's plane words as stored (32-bit
+ * patterns: -0.0 is not 0.0): a 64-bit tag from two modular row hashes picks the slot and filters, and
+ * a hit needs all plane words equal (csrc/nn/eval_cache.h states the definition, csrc/nn/eval_cache.hip
+ * holds the three kernels).  A call goes through in chunks of 2,048 rows: probe (hits are copied out,
+ * misses claim their slot: the newest chunk, and in it the lowest row, wins), compact (the missed rows
+ * gathered), the net's ordinary forward of the missed rows alone -- none when every row hit -- and fill
+ * (outputs delivered, the claim's holder writes the entry).  Which rows hit is a function of the
+ * sequence of calls, `entries` and the chunk size alone (galvanise_zero_amd/util/evalcache.py is the
+ * model).  Rows of one chunk with equal planes all miss: nothing is deduplicated inside a call.
+ * Entries belong to one weight generation of the net: gz_net_set_weights, gz_net_set_weights_device (a
+ * live runner's roll included) and a change of gz_net_set_output_logits flush the cache at its next
+ * call, and a call that a roll from another thread lands in is redone uncached, so every row of a call
+ * comes from the one generation its forward was issued under.  A net's shadow sees the rows the inner
+ * forward computes.
+ * Environment, read at creation (tests): GZ_EVAL_CACHE_TAG_BITS (0..64) lowers the tag bits a probe
+ * compares -- at 0 the plane compare alone separates keys; GZ_EVAL_CACHE_CHUNK_ROWS lowers the rows
+ * per chunk.
+ * Refusals ("eval cache: ..."), before any device call: a null argument; entries < 1; a table over
+ * 16 GiB (the message names the bytes); a call with a cache made for another net or device -- the net
+ * stays usable. */
+typedef struct gz_eval_cache gz_eval_cache;
+struct gz_eval_cache_stats {
+    long calls;            /* gz_net_forward_cached / _device calls of at least one row */
+    long rows;             /* rows of those calls = hits + forward_rows */
+    long hits;             /* rows answered from the table */
+    long forward_rows;     /* rows that went through the net's forward */
+    long inserts;          /* entries written (device counter) */
+    long replaced;         /* of those, over a valid entry of another key (device counter) */
+    long flushes;          /* gz_eval_cache_clear, weight generations, output-logits changes */
+    long entries;
+    long entry_bytes;      /* bytes of one entry: header, planes, outputs */
+};
+gz_eval_cache* gz_eval_cache_create(gz_net* net, long entries);
+void gz_eval_cache_destroy(gz_eval_cache* cache);
+/* a flush: O(1), every entry becomes invalid */
+int gz_eval_cache_clear(gz_eval_cache* cache);
+/* waits for the cache's last call to finish on the device; reset != 0: the counts start from zero */
+int gz_eval_cache_stats(gz_eval_cache* cache, struct gz_eval_cache_stats* out, int reset);
+/* Synchronous, host buffers as gz_net_forward, on the net's own stream. */
+int gz_net_forward_cached(gz_net* net, gz_eval_cache* cache, const float* planes, int n, float* const* policies, float* values);
+/* On the caller's stream, device buffers as gz_net_forward_device; the outputs are complete in stream
+ * order.  Blocks the calling thread once per chunk, until the chunk's count of misses has arrived (the
+ * forward's grid is sized on the host).  Calls on one cache are serialised by a mutex and ordered on
+ * the device by an event the cache owns. */
+int gz_net_forward_cached_device(gz_net* net, gz_eval_cache* cache, void* stream, const float* d_planes, int n,
+                                 float* const* d_policies, float* d_values);
+/* hit[i] = 1 where row i of planes [n][plane_elems] (host memory, or device memory when device_ptr)
+ * would hit now; no claim, no copy, no flush.  For tests and diagnostics.  Synchronous. */
+int gz_eval_cache_probe(gz_eval_cache* cache, int device_ptr, const float* planes, int n, int* hit);
+
 /* Diagnostics: with GZ_KERNEL_STAMPS set in the environment, gz_net_forward records per-workgroup
  * s_memtime stamps at phase boundaries; out8[0] = workgroups averaged, out8[1..4] = their mean
  * cycles of (input + initial conv, residual trunk, head 1x1 convs + features, fused dense heads)
@@ -423,6 +476,18 @@ gz_runner* gz_runner_create(gz_net* net, const struct gz_sm* sm, const struct gz
 int gz_runner_set_symmetry(gz_runner* r, gz_symmetry* s, unsigned salt);
 /* rows that went through the pick path (equal to gz_runner_stats.rows with a symmetry set, else 0) */
 long gz_runner_sym_pick_rows(gz_runner* r);
+/* Self-play through an evaluation cache (gz_eval_cache, above): a launch becomes plane copy -> probe +
+ * compact on the launch stream -> the launcher waits for the count of misses (the older launch retires
+ * meanwhile) -> the forward of the missed rows alone -> fill.  The rows' destinations are the segments
+ * the launch would have written (the pools' pinned buffers, or the output staging's blocks, which are
+ * then copied as always); an all-hit launch records its events without a forward, and a launch's
+ * trunk time is its whole cached time.  A generation roll is applied on the launcher thread, so the
+ * next launch flushes the cache.  Before gz_runner_start only.  Refused ("runner: ..." / "eval cache:
+ * ..."), before any device call: a started runner; a zero-copy runner (GZ_RUNNER_ZERO_COPY=1); a runner
+ * with a symmetry set (and gz_runner_set_symmetry on a runner with a cache); a cache made for another
+ * net.  The cache must outlive the runner.  Without this call the launcher issues exactly the calls it
+ * always did. */
+int gz_runner_set_cache(gz_runner* r, gz_eval_cache* cache);
 int gz_runner_start(gz_runner* r);   /* once per runner: a stopped runner cannot be restarted */
 int gz_runner_wait_batches(gz_runner* r, long total_batches, double timeout_s);
 int gz_runner_wait_rows(gz_runner* r, long total_rows, double timeout_s);
