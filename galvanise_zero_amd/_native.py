@@ -219,6 +219,14 @@ def nn_lib():
             lib.gz_net_forward_cached_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                          ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]
             lib.gz_eval_cache_probe.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, _IP]
+        if hasattr(lib, "gz_net_forward_sym_canon"):   # (absent from older A/B builds loaded through GZ_LIB_DIR)
+            lib.gz_net_forward_sym_canon.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p, _FP,
+                                                     ctypes.c_int, ctypes.POINTER(_FP), _FP]
+            lib.gz_net_forward_sym_canon_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p,
+                                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                            ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]
+            lib.gz_symmetry_canon.argtypes = [ctypes.c_void_p, ctypes.c_uint, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, _IP,
+                                              ctypes.POINTER(ctypes.c_ulonglong)]
         lib._gz_typed = True
     return lib
 
@@ -422,16 +430,24 @@ class HipNet(object):
         """A HipEvalCache of `entries` entries for this net (gz_eval_cache_create)."""
         return HipEvalCache(self, entries)
 
-    def forward(self, planes, symmetry=None, pick=None, cache=None):
+    def forward(self, planes, symmetry=None, pick=None, cache=None, canonical=None):
         """cache: None, or a HipEvalCache (make_cache): rows evaluated before are answered from the
         table, the others go through the forward and are stored (gz_net_forward_cached) -- the same
-        bits either way.  Not together with symmetry=.
+        bits either way.  Not together with symmetry=, unless canonical= is given.
         symmetry: None, or a HipSymmetry (make_symmetry): the forward averaged over its board
         symmetries (gz_net_forward_sym, include/gzero_nn.h).  pick: None for that ensemble, or a
         32-bit salt: each row evaluated under ONE element of the tables, hashed on the GPU from the
         row's own planes and the salt, its policies mapped back (gz_net_forward_sym_pick) -- one
-        forward, bit for bit the plain forward of the permuted row read through the move table."""
-        if cache is not None and symmetry is not None:
+        forward, bit for bit the plain forward of the permuted row read through the move table.
+        canonical: None, or a 32-bit salt: each row evaluated under the element that maps it to its
+        symmetry class's canonical image (gz_net_forward_sym_canon; util.symmetry.canonical_forward
+        is the numpy statement), so that symmetric positions share one image -- and, with cache=, one
+        entry.  Not together with pick=."""
+        if canonical is not None and pick is not None:
+            raise ValueError("canonical= together with pick=: one element per row, chosen one way")
+        if canonical is not None and symmetry is None:
+            raise ValueError("canonical=%r needs symmetry=" % (canonical,))
+        if cache is not None and symmetry is not None and canonical is None:
             raise ValueError("cache= together with symmetry=: the two do not compose")
         d = self.desc
         planes = np.ascontiguousarray(planes, dtype=np.float32)
@@ -440,6 +456,11 @@ class HipNet(object):
         pols = [np.empty((n, p), dtype=np.float32) for p in d.policy_dist_count]
         val = np.empty((n, d.num_values), dtype=np.float32)
         arr = (_FP * len(pols))(*[_fptr(p) for p in pols])
+        if canonical is not None:
+            self._check(self.lib.gz_net_forward_sym_canon(self.handle, symmetry.handle, int(canonical) & 0xFFFFFFFF,
+                                                          cache.handle if cache is not None else None, _fptr(planes), n, arr,
+                                                          _fptr(val)), "gz_net_forward_sym_canon")
+            return pols + [val]
         if cache is not None:
             self._check(self.lib.gz_net_forward_cached(self.handle, cache.handle, _fptr(planes), n, arr, _fptr(val)),
                         "gz_net_forward_cached")
@@ -516,6 +537,33 @@ class HipNet(object):
         self._check(self.lib.gz_symmetry_picks(symmetry.handle, int(salt) & 0xFFFFFFFF, dev, ctypes.c_void_p(ptr), n,
                                                out.ctypes.data_as(_IP)), "gz_symmetry_picks")
         return out
+
+    def forward_sym_canon_device(self, symmetry, salt, cache, stream, d_planes, n, d_policies, d_values):
+        """gz_net_forward_sym_canon_device: the canonical-orientation forward on `stream` (cache: a
+        HipEvalCache or None), device pointers as forward_device.  One HipSymmetry serves one stream at
+        a time (its scratch); with a cache the call blocks once per chunk, as forward_cached_device."""
+        arr = (ctypes.c_void_p * len(d_policies))(*d_policies)
+        self._check(self.lib.gz_net_forward_sym_canon_device(self.handle, symmetry.handle, int(salt) & 0xFFFFFFFF,
+                                                             cache.handle if cache is not None else None,
+                                                             ctypes.c_void_p(stream), ctypes.c_void_p(d_planes), n, arr,
+                                                             ctypes.c_void_p(d_values)),
+                    "gz_net_forward_sym_canon_device")
+
+    def symmetry_canon(self, symmetry, salt, planes=None, device_ptr=None, n=None):
+        """(g, tags) of each row as the GPU kernel computes them (gz_symmetry_canon): planes a host
+        array [n, ...], or device_ptr + n.  util.symmetry.canonical_elements is the numpy statement."""
+        if planes is not None:
+            planes = np.ascontiguousarray(planes, dtype=np.float32)
+            n, ptr, dev = planes.shape[0], planes.ctypes.data, 0
+            assert planes.size == n * symmetry.plane_src.shape[1]
+        else:
+            ptr, dev = device_ptr, 1
+        g = np.empty(n, dtype=np.int32)
+        tags = np.empty(n, dtype=np.uint64)
+        self._check(self.lib.gz_symmetry_canon(symmetry.handle, int(salt) & 0xFFFFFFFF, dev, ctypes.c_void_p(ptr), n,
+                                               g.ctypes.data_as(_IP), tags.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong))),
+                    "gz_symmetry_canon")
+        return g, tags
 
     def forward_segments(self, stream, segments):
         """Asynchronous segmented launch on `stream`: segments = [(rows, planes_ptr, [policy_ptr per
@@ -885,6 +933,8 @@ def runner_lib():
             lib.gz_runner_set_symmetry.argtypes = [_VP, _VP, ctypes.c_uint]
             lib.gz_runner_sym_pick_rows.restype = ctypes.c_long
             lib.gz_runner_sym_pick_rows.argtypes = [_VP]
+        if hasattr(lib, "gz_runner_set_canonical"):   # (absent from older A/B builds loaded through GZ_LIB_DIR)
+            lib.gz_runner_set_canonical.argtypes = [_VP, _VP, ctypes.c_uint, _VP]
         lib._gz_runner_typed = True
     return lib
 

@@ -49,30 +49,8 @@ namespace gzcache {
 constexpr int kMaxChunkRows = 2048;              // < 1 << 16: a row's index fits the claim word
 constexpr long long kMaxTableBytes = 16ll << 30; // gz_eval_cache_create refuses a larger table
 
-GZSYM_HD inline unsigned mix32b(unsigned x) {
-    x ^= x >> 15;
-    x *= 0x2c1b3c6du;
-    x ^= x >> 12;
-    x *= 0x297a2d39u;
-    x ^= x >> 15;
-    return x;
-}
-
-// element i's term of the second row hash (the first is gzsym::pick_term)
-GZSYM_HD inline unsigned hash2_term(unsigned bits, unsigned i) { return mix32b(bits + 0x85EBCA77u * (i + 1u)); }
-
-GZSYM_HD inline unsigned long long make_tag(unsigned h1, unsigned h2) {
-    return ((unsigned long long)h2 << 32) | (unsigned long long)h1;
-}
-
-GZSYM_HD inline unsigned long long mix64(unsigned long long x) {
-    x ^= x >> 30;
-    x *= 0xbf58476d1ce4e5b9ull;
-    x ^= x >> 27;
-    x *= 0x94d049bb133111ebull;
-    x ^= x >> 31;
-    return x;
-}
+// mix32b, hash2_term, make_tag and mix64 are in symmetry.h (namespace gzcache): the canonical
+// orientation there ranks a row's images by this tag.
 
 GZSYM_HD inline unsigned long long slot_of(unsigned long long tag, unsigned long long N) { return mix64(tag) % N; }
 

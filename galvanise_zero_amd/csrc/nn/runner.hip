@@ -124,6 +124,9 @@ struct gz_runner {
     // gz_runner_set_cache: every launch goes through the evaluation cache (csrc/nn/eval_cache.h): the
     // rows that hit are answered from the table, the others alone go through the forward; null: none
     gz_eval_cache* cache = nullptr;
+    // gz_runner_set_canonical: sym (and, if given, cache) set together, the element being the one
+    // that maps a row to its class's canonical image; the cache then reads the permuted planes
+    bool canon = false;
     Compose compose = kSplit;
     Batch batches_ring[2];
 
@@ -583,7 +586,10 @@ static void launcher_main(gz_runner* r) {
                     }
                     b.d_sym_cap = cap;
                 }
-                if (gzsym::pick_expand_launch(r->sym, r->stream, r->sym_salt, b.d_planes, b.rows, b.d_picks, b.d_sym_planes) != 0) {
+                if ((r->canon ? gzsym::canon_expand_launch(r->sym, r->stream, r->sym_salt, b.d_planes, b.rows, b.d_picks, nullptr,
+                                                           b.d_sym_planes)
+                              : gzsym::pick_expand_launch(r->sym, r->stream, r->sym_salt, b.d_planes, b.rows, b.d_picks,
+                                                          b.d_sym_planes)) != 0) {
                     set_failed(r, std::string("symmetry pick launch failed: ") + gz_nn_last_error());
                     return;
                 }
@@ -640,7 +646,8 @@ static void launcher_main(gz_runner* r) {
             // probe + compact, the count of misses, the forward of the misses alone, fill: the rows'
             // destinations are the segments' (the pools' pinned buffers, or the d_out blocks); an
             // all-hit launch records its events without a forward (evm at the end: there is no trunk
-            // launch to time apart)
+            // launch to time apart).  In canonical mode the cache reads the permuted planes and the
+            // segments are the raw outputs the gather below reads.
             gzsym::PickSegments ps{};
             ps.nseg = (int)segs.size();
             int row = 0;
@@ -651,7 +658,8 @@ static void launcher_main(gz_runner* r) {
                 ps.out[k][r->num_policies] = segs[k].values;
             }
             if (hipEventRecord(b.ev0, r->stream) != hipSuccess ||
-                gzcache::cached_launch(r->net, r->cache, r->stream, b.d_planes, b.rows, ps, idle, &idle_ctx) != 0 ||
+                gzcache::cached_launch(r->net, r->cache, r->stream, r->sym ? b.d_sym_planes : b.d_planes, b.rows, ps, idle,
+                                       &idle_ctx) != 0 ||
                 hipEventRecord(b.evm, r->stream) != hipSuccess) {
                 set_failed(r, std::string("cached launch failed: ") + gz_nn_last_error());
                 return;
@@ -836,6 +844,10 @@ extern "C" int gz_runner_set_symmetry(gz_runner* r, gz_symmetry* s, unsigned sal
         g_err = "runner: gz_runner_set_symmetry on a zero-copy runner (GZ_RUNNER_ZERO_COPY=1): the pick reads the HBM plane staging";
         return -1;
     }
+    if (r->canon) {
+        g_err = "runner: gz_runner_set_symmetry on a runner in canonical mode (gz_runner_set_canonical set its symmetry)";
+        return -1;
+    }
     if (r->cache) {
         g_err = "runner: gz_runner_set_symmetry on a runner with an evaluation cache (the two do not compose)";
         return -1;
@@ -876,6 +888,10 @@ extern "C" int gz_runner_set_cache(gz_runner* r, gz_eval_cache* c) {
         g_err = "runner: gz_runner_set_cache on a zero-copy runner (GZ_RUNNER_ZERO_COPY=1): the probe reads the HBM plane staging";
         return -1;
     }
+    if (r->canon) {
+        g_err = "runner: gz_runner_set_cache on a runner in canonical mode (gz_runner_set_canonical takes the cache)";
+        return -1;
+    }
     if (r->sym) {
         g_err = "runner: gz_runner_set_cache on a runner with a symmetry (the two do not compose)";
         return -1;
@@ -885,6 +901,47 @@ extern "C" int gz_runner_set_cache(gz_runner* r, gz_eval_cache* c) {
         return -1;
     }
     r->cache = c;
+    return 0;
+}
+
+// The canonical orientation from now on, through `c` when given (include/gzero_nn.h).  Every refusal
+// precedes the first device call.
+extern "C" int gz_runner_set_canonical(gz_runner* r, gz_symmetry* s, unsigned salt, gz_eval_cache* c) {
+    if (!r || !s) {
+        g_err = "runner: null argument";
+        return -1;
+    }
+    if (r->started) {
+        g_err = "runner: gz_runner_set_canonical after gz_runner_start (set the canonical mode before the runner starts)";
+        return -1;
+    }
+    if (r->zero_copy) {
+        g_err = "runner: gz_runner_set_canonical on a zero-copy runner (GZ_RUNNER_ZERO_COPY=1): the kernel reads the HBM plane staging";
+        return -1;
+    }
+    if (r->canon || r->sym || r->cache) {
+        g_err = std::string("runner: gz_runner_set_canonical on a runner that already has ") +
+                (r->canon ? "a canonical setting" : r->sym ? "a symmetry" : "an evaluation cache");
+        return -1;
+    }
+    gzsym::NetView v;
+    if (gzsym::pick_check(r->net, s, &v) != 0 || (c && gzcache::runner_check(r->net, c) != 0)) {
+        g_err = gz_nn_last_error();
+        return -1;
+    }
+    if (hipSetDevice(r->cfg.device) != hipSuccess || gzsym::pick_prepare(s, v) != 0) {
+        g_err = std::string("runner: symmetry tables: ") + gz_nn_last_error();
+        return -1;
+    }
+    if (!r->out_stream && hipStreamCreateWithFlags(&r->out_stream, hipStreamNonBlocking) != hipSuccess) {
+        g_err = "runner: stream creation failed";
+        return -1;
+    }
+    r->out_staging = true;           // as gz_runner_set_symmetry: the gather writes the slot's d_out
+    r->sym = s;
+    r->sym_salt = salt;
+    r->cache = c;
+    r->canon = true;
     return 0;
 }
 

@@ -24,6 +24,10 @@
 // Below the ensemble: one symmetry per row, picked from a hash of the row's own planes
 // (gz_net_forward_sym_pick, gz_runner_set_symmetry) -- the definition, likewise as functions a CPU
 // program runs (tests/symmetry_pick_host_check.cpp).
+//
+// Below the pick: the canonical orientation (gz_net_forward_sym_canon, gz_runner_set_canonical) -- the
+// element is the one that maps the row to its symmetry class's canonical image, so symmetric
+// positions share one forward and one cache entry (tests/symmetry_canon_host_check.cpp).
 #pragma once
 
 #include <cstddef>
@@ -153,6 +157,104 @@ GZSYM_HD inline int pick_find_segment(const PickSegments& sg, int row) {
     return s;
 }
 
+}  // namespace gzsym
+
+// The evaluation cache's row tag (eval_cache.h states the cache; these four are here because the
+// canonical orientation below ranks a row's images by that tag).
+namespace gzcache {
+
+GZSYM_HD inline unsigned mix32b(unsigned x) {
+    x ^= x >> 15;
+    x *= 0x2c1b3c6du;
+    x ^= x >> 12;
+    x *= 0x297a2d39u;
+    x ^= x >> 15;
+    return x;
+}
+
+// element i's term of the second row hash (the first is gzsym::pick_term)
+GZSYM_HD inline unsigned hash2_term(unsigned bits, unsigned i) { return mix32b(bits + 0x85EBCA77u * (i + 1u)); }
+
+GZSYM_HD inline unsigned long long make_tag(unsigned h1, unsigned h2) {
+    return ((unsigned long long)h2 << 32) | (unsigned long long)h1;
+}
+
+GZSYM_HD inline unsigned long long mix64(unsigned long long x) {
+    x ^= x >> 30;
+    x *= 0xbf58476d1ce4e5b9ull;
+    x ^= x >> 27;
+    x *= 0x94d049bb133111ebull;
+    x ^= x >> 31;
+    return x;
+}
+
+}  // namespace gzcache
+
+namespace gzsym {
+
+// ---- canonical orientation: every member of a symmetry class evaluated as the same image -----------
+// (gz_net_forward_sym_canon, gz_runner_set_canonical).  For a row X of E plane words as 32-bit patterns
+// (pick_term's reading), tables of S <= 8 elements and a 32-bit salt:
+//
+//   X_s[i] = X[plane_src[s][i]]                                  image s, s in [0, S)
+//   t_s    = make_tag(pick_hash(X_s), hash2(X_s))                the cache's 64-bit row tag of image s
+//   k_s    = mix64(t_s ^ uint64(salt))                           a bijection of the tag: another salt,
+//                                                                another representative
+//   g      = the s with the smallest (k_s, s)                    ties, equal images included: lowest s
+//   X'     = X_g;  p', v' = the net's ordinary forward of X'     or, with a cache, the cached forward
+//   out_r[m] = p'_r[move_src[r][g][m]];  values = v'             sym_pick_gather_kernel, unchanged
+//
+// Both hashes are modular sums, so sym_canon_expand_kernel's reduction tree and the loops below agree.
+//
+// 1. No floating-point operation is added.  g depends on the row, the tables and the salt alone: a
+//    row is bit for bit the plain forward of X_g read through move_src[g], in any batch, chunk, entry
+//    point or replay.  S = 1 with the identity is gz_net_forward.  Tables that are no group are served;
+//    they get this property and nothing more.
+// 2. Symmetric positions share one image.  Where the tables are closed under composition (every
+//    game's are), the images of Y = X_t are the images of X, so both rows get the same X' -- through a
+//    cache the second one hits -- and, if X's S images are all distinct,
+//    out_X[r][m] == out_Y[r][move_src[r][t][m]] exactly for every t and m (by
+//    move_src[c] = move_src[b][move_src[a]] for c = "a then b").  The ensemble gives that to 1e-6 only.
+// 3. A position that is its own image (X_s == X_t, s != t) is evaluated correctly, under the lowest
+//    such s; property 2's equality is not promised for it (a net's output on a symmetric board need
+//    not be symmetric).  A tag collision between different images (2^-64 a pair) can cost sharing,
+//    never correctness: the cache's compare of all plane words decides alone.
+GZSYM_HD inline unsigned long long canon_key(unsigned long long tag, unsigned salt) {
+    return gzcache::mix64(tag ^ (unsigned long long)salt);
+}
+
+// g from the S images' hash totals (h1[s], h2[s]); *tag = t_g
+GZSYM_HD inline int canon_pick(const unsigned* h1, const unsigned* h2, int S, unsigned salt, unsigned long long* tag) {
+    int g = 0;
+    unsigned long long best_tag = gzcache::make_tag(h1[0], h2[0]);
+    unsigned long long best = canon_key(best_tag, salt);
+    for (int s = 1; s < S; ++s) {
+        const unsigned long long t = gzcache::make_tag(h1[s], h2[s]), k = canon_key(t, salt);
+        if (k < best) { best = k; best_tag = t; g = s; }
+    }
+    *tag = best_tag;
+    return g;
+}
+
+// the definition, serially: g of one row; *tag (may be null) = t_g
+inline int canon_element(const unsigned* bits, int E, int S, const int* plane_src, unsigned salt, unsigned long long* tag) {
+    unsigned h1[kMaxCount] = {}, h2[kMaxCount] = {};
+    for (int s = 0; s < S; ++s)
+        for (int i = 0; i < E; ++i) {
+            const unsigned b = bits[plane_src[(size_t)s * E + i]];
+            h1[s] += pick_term(b, (unsigned)i);
+            h2[s] += gzcache::hash2_term(b, (unsigned)i);
+        }
+    unsigned long long t = 0;
+    const int g = canon_pick(h1, h2, S, salt, &t);
+    if (tag) *tag = t;
+    return g;
+}
+
+// sym_canon_expand_kernel keeps a row in LDS when it has at most this many words (32 KiB: five
+// workgroups a CU; the largest game here has 5,415); a longer row is gathered from global memory
+constexpr int kCanonLdsWords = 8192;
+
 // true when t[0 .. len) holds every value of 0 .. len - 1 once; else *bad = the first offending entry
 inline bool is_permutation(const int* t, int len, int* bad) {
     std::vector<char> seen((size_t)len, 0);
@@ -224,6 +326,10 @@ int pick_prepare(gz_symmetry* s, const NetView& v);
 int pick_expand_launch(gz_symmetry* s, hipStream_t stream, unsigned salt, const float* d_in, int n, int* d_picks, float* d_x);
 int pick_gather_launch(gz_symmetry* s, hipStream_t stream, const int* d_picks, int n, const float* const* d_raw,
                        const PickSegments& segs);
+// canon_expand_launch: pick_expand_launch with the canonical g (sym_canon_expand_kernel); d_tags (may
+// be null) receives each row's t_g.  The gather is the pick's.
+int canon_expand_launch(gz_symmetry* s, hipStream_t stream, unsigned salt, const float* d_in, int n, int* d_picks,
+                        unsigned long long* d_tags, float* d_x);
 #endif
 
 }  // namespace gzsym

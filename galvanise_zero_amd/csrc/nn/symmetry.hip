@@ -1,6 +1,9 @@
 // The symmetry ensemble's two kernels and entry points, and below them the two kernels and entry
 // points of the one-symmetry-per-row pick (symmetry.h states the arithmetic of both; the net's own
-// forward runs between the kernels, unchanged, through gz_net_forward_device).
+// forward runs between the kernels, unchanged, through gz_net_forward_device).  Last, the canonical
+// orientation: its expand kernel and entry points (the gather is the pick's; with a cache the cached
+// forward of eval_cache.hip runs between the kernels instead).
+#include "eval_cache.h"
 #include "symmetry.h"
 
 #include <hip/hip_runtime.h>
@@ -452,5 +455,227 @@ extern "C" int gz_symmetry_picks(gz_symmetry* s, unsigned salt, int device_ptr, 
     }
     (void)hipFree(mem);
     if (e != hipSuccess) return set_error(std::string("symmetry: picks: ") + hipGetErrorString(e));
+    return 0;
+}
+
+// ---- canonical orientation (symmetry.h states the definition) -------------------------------------
+
+__device__ inline unsigned canon_wave_sum(unsigned v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += (unsigned)__shfl_xor((int)v, d, 64);
+    return v;
+}
+
+// One workgroup per row.  kLds: the row is read once into LDS (16-byte loads where the row is 16-byte
+// aligned, a scalar loop otherwise and for the tail) and every image is gathered from there; else
+// (a row over kCanonLdsWords) the images are gathered from global memory.  Thread tid takes elements
+// tid, tid + 256, ... of every image -- the tables are read coalesced -- and keeps the 2 S partial
+// sums of the two hashes; wave shuffles, then the four waves through LDS, give the totals, from which
+// every thread computes g (canon_pick).  picks[row] = g, tags[row] = t_g (tags may be null), and the
+// row permuted through plane_src[g] to x (x == nullptr: g and the tag alone).
+template <bool kLds>
+__global__ void __launch_bounds__(256) sym_canon_expand_kernel(const float* __restrict__ in, float* __restrict__ x,
+                                                               int* __restrict__ picks, unsigned long long* __restrict__ tags,
+                                                               int n, int E, int S, unsigned salt,
+                                                               const int* __restrict__ plane_src) {
+    extern __shared__ uint4 canon_row4[];        // kLds: the row's E words
+    __shared__ unsigned part[4][2 * kMaxCount];
+    __shared__ unsigned tot[2 * kMaxCount];      // h1 of elements 0 .. 7, then h2
+    // static LDS precedes the dynamic region unpadded: its size keeps the row's 16-byte stores aligned
+    static_assert((sizeof(part) + sizeof(tot)) % 16 == 0, "the dynamic LDS row must start 16-byte aligned");
+    const int row = blockIdx.x, tid = threadIdx.x;
+    if (row >= n) return;
+    const unsigned* b = (const unsigned*)in + (size_t)row * E;
+    const unsigned* src = b;
+    if (kLds) {
+        unsigned* lrow = (unsigned*)canon_row4;
+        int done = 0;
+        if (((uintptr_t)b & 15) == 0) {
+            const int n4 = E >> 2;
+            for (int i4 = tid; i4 < n4; i4 += 256) canon_row4[i4] = ((const uint4*)b)[i4];
+            done = n4 << 2;
+        }
+        for (int i = done + tid; i < E; i += 256) lrow[i] = b[i];
+        __syncthreads();
+        src = lrow;
+    }
+    unsigned h1[kMaxCount] = {}, h2[kMaxCount] = {};
+    for (int i = tid; i < E; i += 256) {
+#pragma unroll
+        for (int s = 0; s < kMaxCount; ++s)
+            if (s < S) {
+                const unsigned v = src[plane_src[(size_t)s * E + i]];
+                h1[s] += pick_term(v, (unsigned)i);
+                h2[s] += gzcache::hash2_term(v, (unsigned)i);
+            }
+    }
+#pragma unroll
+    for (int s = 0; s < kMaxCount; ++s)
+        if (s < S) {                             // (uniform)
+            h1[s] = canon_wave_sum(h1[s]);
+            h2[s] = canon_wave_sum(h2[s]);
+        }
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int s = 0; s < kMaxCount; ++s) {
+            part[tid >> 6][s] = h1[s];
+            part[tid >> 6][kMaxCount + s] = h2[s];
+        }
+    }
+    __syncthreads();
+    if (tid < 2 * kMaxCount) tot[tid] = part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid];
+    __syncthreads();
+    unsigned long long tag;
+    const int g = canon_pick(tot, tot + kMaxCount, S, salt, &tag);
+    if (tid == 0) {
+        picks[row] = g;
+        if (tags) tags[row] = tag;
+    }
+    if (!x) return;
+    for (int i = tid; i < E; i += 256) x[(size_t)row * E + i] = __uint_as_float(src[plane_src[(size_t)g * E + i]]);
+}
+
+static int canon_launch(hipStream_t stream, unsigned salt, const float* d_in, int n, int E, int S, const int* d_plane,
+                        int* d_picks, unsigned long long* d_tags, float* d_x) {
+    if (n <= 0) return 0;
+    if (E <= kCanonLdsWords)
+        sym_canon_expand_kernel<true><<<dim3((unsigned)n), dim3(256), (((size_t)E + 3) & ~(size_t)3) * 4, stream>>>(
+            d_in, d_x, d_picks, d_tags, n, E, S, salt, d_plane);
+    else
+        sym_canon_expand_kernel<false><<<dim3((unsigned)n), dim3(256), 0, stream>>>(d_in, d_x, d_picks, d_tags, n, E, S, salt,
+                                                                                    d_plane);
+    SYMCHK(hipGetLastError());
+    return 0;
+}
+
+int gzsym::canon_expand_launch(gz_symmetry* s, hipStream_t stream, unsigned salt, const float* d_in, int n, int* d_picks,
+                               unsigned long long* d_tags, float* d_x) {
+    return canon_launch(stream, salt, d_in, n, s->E, s->L.S, s->d_plane, d_picks, d_tags, d_x);
+}
+
+// the refusals of a canonical forward, no device call: the pick's, and with a cache the cache's
+static int canon_check(gz_net* net, gz_symmetry* s, gz_eval_cache* cache, NetView* v) {
+    if (pick_check(net, s, v)) return -1;
+    return cache ? gzcache::runner_check(net, cache) : 0;
+}
+
+// pick_chunks with the canonical expand; between expand and gather the net's forward of the canonical
+// planes, or with a cache one cached call of them, its one segment the raw scratch
+static int canon_chunks(gz_net* net, gz_symmetry* s, const NetView& v, unsigned salt, gz_eval_cache* cache, hipStream_t stream,
+                        const float* d_planes, int n, float* const* d_pol, float* d_val) {
+    const int E = s->E;
+    const int chunk = chunk_rows(1, env_chunk_rows());
+    if (ensure_tables(s, v)) return -1;
+    const int rows = std::min(n, chunk);
+    if (ensure_scratch(s, (size_t)rows * (row_floats(s) + 1))) return -1;   // + 1: the row's element
+    for (int r0 = 0; r0 < n; r0 += chunk) {
+        const int c = std::min(chunk, n - r0);
+        float* x = s->d_scratch;
+        float* raw[GZ_MAX_ROLES + 1];
+        float* p = x + (size_t)c * E;
+        PickSegments sg{}, rawsg{};
+        sg.nseg = rawsg.nseg = 1;
+        sg.row0[0] = rawsg.row0[0] = 0;
+        for (int r = 0; r < s->L.R; ++r) {
+            raw[r] = p;
+            rawsg.out[0][r] = p;
+            sg.out[0][r] = d_pol[r] + (size_t)r0 * s->L.P[r];
+            p += (size_t)c * s->L.P[r];
+        }
+        raw[s->L.R] = p;
+        rawsg.out[0][s->L.R] = p;
+        sg.out[0][s->L.R] = d_val + (size_t)r0 * s->L.V;
+        int* picks = (int*)(p + (size_t)c * s->L.V);
+        if (canon_expand_launch(s, stream, salt, d_planes + (size_t)r0 * E, c, picks, nullptr, x)) return -1;
+        if (cache) {
+            if (gzcache::cached_launch(net, cache, stream, x, c, rawsg, nullptr, nullptr)) return -1;
+        } else if (gz_net_forward_device(net, stream, x, c, raw, raw[s->L.R])) {
+            return -1;
+        }
+        if (pick_gather_launch(s, stream, picks, c, raw, sg)) return -1;
+    }
+    return 0;
+}
+
+extern "C" int gz_net_forward_sym_canon_device(gz_net* net, gz_symmetry* s, unsigned salt, gz_eval_cache* cache, void* stream,
+                                               const float* d_planes, int n, float* const* d_policies, float* d_values) {
+    if (!net || !s || !d_planes || !d_policies || !d_values) return set_error("symmetry: null argument");
+    NetView v;
+    if (canon_check(net, s, cache, &v)) return -1;
+    if (n <= 0) return 0;
+    return canon_chunks(net, s, v, salt, cache, (hipStream_t)stream, d_planes, n, d_policies, d_values);
+}
+
+extern "C" int gz_net_forward_sym_canon(gz_net* net, gz_symmetry* s, unsigned salt, gz_eval_cache* cache, const float* planes,
+                                        int n, float* const* policies, float* values) {
+    if (!net || !s || !planes || !policies || !values) return set_error("symmetry: null argument");
+    NetView v;
+    if (canon_check(net, s, cache, &v)) return -1;
+    if (n <= 0) return 0;
+    std::lock_guard<std::mutex> lk(s->mu);
+    hipStream_t stream = (hipStream_t)v.host_stream;
+    const int chunk = chunk_rows(1, env_chunk_rows());
+    if (ensure_tables(s, v) || ensure_io(s, std::min(n, chunk))) return -1;
+    const size_t E = (size_t)s->E;
+    for (int r0 = 0; r0 < n; r0 += chunk) {
+        const int c = std::min(chunk, n - r0);
+        float* d_in = s->d_io;
+        float* d_pol[GZ_MAX_ROLES];
+        float* p = d_in + (size_t)c * E;
+        for (int r = 0; r < s->L.R; ++r) { d_pol[r] = p; p += (size_t)c * s->L.P[r]; }
+        float* d_val = p;
+        SYMCHK(hipMemcpyAsync(d_in, planes + (size_t)r0 * E, (size_t)c * E * sizeof(float), hipMemcpyHostToDevice, stream));
+        if (canon_chunks(net, s, v, salt, cache, stream, d_in, c, d_pol, d_val)) return -1;
+        for (int r = 0; r < s->L.R; ++r)
+            SYMCHK(hipMemcpyAsync(policies[r] + (size_t)r0 * s->L.P[r], d_pol[r], (size_t)c * s->L.P[r] * sizeof(float),
+                                  hipMemcpyDeviceToHost, stream));
+        SYMCHK(hipMemcpyAsync(values + (size_t)r0 * s->L.V, d_val, (size_t)c * s->L.V * sizeof(float), hipMemcpyDeviceToHost,
+                              stream));
+    }
+    SYMCHK(hipStreamSynchronize(stream));
+    return 0;
+}
+
+// g and t_g of each row as sym_canon_expand_kernel computes them (no net: the planes and the plane
+// table alone).  Synchronous, on the null stream, through buffers of its own.
+extern "C" int gz_symmetry_canon(gz_symmetry* s, unsigned salt, int device_ptr, const float* planes, int n, int* g_out,
+                                 unsigned long long* tag_out) {
+    if (!s || !planes || !g_out) return set_error("symmetry: null argument");
+    if (n <= 0) return 0;
+    std::lock_guard<std::mutex> lk(s->mu);
+    SYMCHK(hipSetDevice(s->device));
+    const size_t E = (size_t)s->E;
+    const int chunk = std::min(n, chunk_rows(1, env_chunk_rows()));
+    auto pad = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t tag_bytes = pad((size_t)chunk * sizeof(unsigned long long)), pick_bytes = pad((size_t)chunk * sizeof(int)),
+                 table_bytes = s->d_plane ? 0 : pad(s->h_plane.size() * sizeof(int));
+    char* mem = nullptr;
+    SYMCHK(hipMalloc((void**)&mem, tag_bytes + pick_bytes + table_bytes + (device_ptr ? 0 : (size_t)chunk * E * sizeof(float))));
+    unsigned long long* d_tags = (unsigned long long*)mem;
+    int* d_picks = (int*)(mem + tag_bytes);
+    const int* d_plane = s->d_plane;
+    float* d_in = (float*)(mem + tag_bytes + pick_bytes + table_bytes);
+    hipError_t e = hipSuccess;
+    if (!d_plane) {                              // (no forward has uploaded the tables yet)
+        e = hipMemcpy(mem + tag_bytes + pick_bytes, s->h_plane.data(), s->h_plane.size() * sizeof(int), hipMemcpyHostToDevice);
+        d_plane = (const int*)(mem + tag_bytes + pick_bytes);
+    }
+    int rc = 0;
+    for (int r0 = 0; r0 < n && e == hipSuccess && rc == 0; r0 += chunk) {
+        const int c = std::min(chunk, n - r0);
+        const float* src = planes + (size_t)r0 * E;
+        if (!device_ptr) {
+            e = hipMemcpy(d_in, src, (size_t)c * E * sizeof(float), hipMemcpyHostToDevice);
+            src = d_in;
+        }
+        if (e != hipSuccess) break;
+        rc = canon_launch(0, salt, src, c, s->E, s->L.S, d_plane, d_picks, d_tags, nullptr);
+        if (rc) break;
+        e = hipMemcpy(g_out + r0, d_picks, (size_t)c * sizeof(int), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && tag_out) e = hipMemcpy(tag_out + r0, d_tags, (size_t)c * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(mem);
+    if (rc) return -1;
+    if (e != hipSuccess) return set_error(std::string("symmetry: canon: ") + hipGetErrorString(e));
     return 0;
 }

@@ -46,13 +46,16 @@ class HipModel(object):
         (HipNet.forward(X, symmetry=..., pick=symmetry_salt)) -- one row per evaluation.
         cache_entries: None, or the entries of an evaluation cache (HipNet.make_cache): predict_on_batch
         answers rows evaluated before from the table, bit for bit what the forward gives
-        (self.cache.stats()).  Not together with symmetries=."""
-        if cache_entries is not None and symmetries is not None:
+        (self.cache.stats()).  Not together with symmetries=, except in the "canonical" mode.
+        symmetry_mode "canonical": every row evaluated under the element that maps it to its symmetry
+        class's canonical image (HipNet.forward(X, symmetry=..., canonical=symmetry_salt, cache=...)),
+        so that symmetric positions share one forward and, with cache_entries, one entry."""
+        if symmetry_mode not in ("average", "pick", "canonical"):
+            raise ValueError('symmetry_mode %r: "average" or "pick" or "canonical"' % (symmetry_mode,))
+        if cache_entries is not None and symmetries is not None and symmetry_mode != "canonical":
             raise ValueError("cache_entries= together with symmetries=: the two do not compose")
-        if symmetry_mode not in ("average", "pick"):
-            raise ValueError('symmetry_mode %r: "average" or "pick"' % (symmetry_mode,))
-        if symmetry_mode == "pick" and symmetries is None:
-            raise ValueError('symmetry_mode "pick" needs symmetries=')
+        if symmetry_mode in ("pick", "canonical") and symmetries is None:
+            raise ValueError('symmetry_mode "%s" needs symmetries=' % symmetry_mode)
         self.desc = desc
         self.weights = weights
         self.net = HipNet(desc, device, precision)
@@ -61,12 +64,15 @@ class HipModel(object):
         self.net.set_weights(to_blob(weights))
         self.symmetry = self.net.make_symmetry(symmetries) if symmetries is not None else None
         self.pick = (int(symmetry_salt) & 0xFFFFFFFF) if symmetry_mode == "pick" else None
+        self.canonical = (int(symmetry_salt) & 0xFFFFFFFF) if symmetry_mode == "canonical" else None
         self.cache = self.net.make_cache(cache_entries) if cache_entries is not None else None
 
     def predict_on_batch(self, X):
         X = np.asarray(X, dtype=np.float32)
         d = self.desc
         assert X.shape[1:] == (d.input_channels, d.input_columns, d.input_rows), X.shape
+        if self.canonical is not None:
+            return self.net.forward(X, symmetry=self.symmetry, canonical=self.canonical, cache=self.cache)
         if self.cache is not None:
             return self.net.forward(X, cache=self.cache)
         return self.net.forward(X, symmetry=self.symmetry, pick=self.pick)

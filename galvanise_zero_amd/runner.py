@@ -13,7 +13,7 @@ class SelfPlayRunner(object):
     def __init__(self, hip_net, sm, transformer, conf, device=0, num_threads=8, pools_per_thread=2,
                  batch_size=256, seed=0, game_index_base=0, keep_samples=False, max_launch_rows=0,
                  spin_yield_playouts=0, min_launch_rows=0, max_launch_wait_us=0, per_pool_unique_states=True,
-                 symmetry=None, symmetry_salt=None, cache=None):
+                 symmetry=None, symmetry_salt=None, cache=None, symmetry_mode="pick"):
         """cache: None, or a _native.HipEvalCache of hip_net (HipNet.make_cache): every launch goes
         through it -- rows evaluated before are answered from the table, the others alone go through
         the forward (gz_runner_set_cache, include/gzero_nn.h); the samples are bit for bit those of a
@@ -21,7 +21,14 @@ class SelfPlayRunner(object):
         symmetry: None, or a _native.HipSymmetry (HipNet.make_symmetry): every leaf is evaluated
         under one element of its tables, picked on the GPU from a hash of the row's own planes and
         symmetry_salt (default: seed & 0xFFFFFFFF), and its policies mapped back
-        (gz_runner_set_symmetry, include/gzero_nn.h).  One forward per leaf, as without."""
+        (gz_runner_set_symmetry, include/gzero_nn.h).  One forward per leaf, as without.
+        symmetry_mode: "pick" (that), or "canonical": the element is the one that maps the leaf to its
+        symmetry class's canonical image, so symmetric positions share one forward and -- cache= is
+        allowed in this mode, and optional -- one cache entry (gz_runner_set_canonical)."""
+        if symmetry_mode not in ("pick", "canonical"):
+            raise ValueError('symmetry_mode %r: "pick" or "canonical"' % (symmetry_mode,))
+        if symmetry_mode == "canonical" and symmetry is None:
+            raise ValueError('symmetry_mode "canonical" needs symmetry=')
         self.lib = _native.runner_lib()
         _native.engine_lib()
         self.net = hip_net
@@ -46,11 +53,25 @@ class SelfPlayRunner(object):
         self.batch_size = batch_size
         self.symmetry = symmetry             # (kept alive: the runner reads its tables)
         self.symmetry_salt = None
+        self.cache = None
+        if symmetry_mode == "canonical":
+            self.set_canonical(symmetry, (seed if symmetry_salt is None else symmetry_salt) & 0xFFFFFFFF, cache)
+            return
         if symmetry is not None:
             self.set_symmetry(symmetry, (seed if symmetry_salt is None else symmetry_salt) & 0xFFFFFFFF)
-        self.cache = None
         if cache is not None:
             self.set_cache(cache)
+
+    def set_canonical(self, symmetry, salt, cache=None):
+        """gz_runner_set_canonical: before start() only."""
+        if not hasattr(self.lib, "gz_runner_set_canonical"):
+            raise RuntimeError("libgz_nn.so has no canonical orientation (an older build)")
+        if self.lib.gz_runner_set_canonical(self.handle, symmetry.handle, int(salt) & 0xFFFFFFFF,
+                                            cache.handle if cache is not None else None) != 0:
+            raise RuntimeError("gz_runner_set_canonical: %s" % self.lib.gz_runner_last_error().decode())
+        self.symmetry = symmetry             # (both kept alive: the launcher uses them)
+        self.symmetry_salt = int(salt) & 0xFFFFFFFF
+        self.cache = cache
 
     def set_cache(self, cache):
         """gz_runner_set_cache: before start() only."""

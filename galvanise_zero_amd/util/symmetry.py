@@ -152,6 +152,43 @@ def pick_forward(forward, X, tables, salt):
     return [np.ascontiguousarray(np.take_along_axis(o, move_src[r][g], axis=1)) for r, o in enumerate(outs[:-1])] + [outs[-1]]
 
 
+def canonical_elements(X, tables, salt):
+    """The table element g under which gz_net_forward_sym_canon evaluates each row of X, and the
+    cache tag of that image (csrc/nn/symmetry.h, "canonical"): with X_s = X[plane_src[s]] and t_s its
+    64-bit row tag (util.evalcache.tags -- the one numpy statement of the tag), g is the s with the
+    smallest (mix64(t_s ^ salt), s).  `tables`: an object with plane_src [S][E], or that array.
+    Returns (int32 [n], uint64 [n])."""
+    from .evalcache import mix64, tags          # (evalcache imports this module)
+    X = np.ascontiguousarray(X, dtype=np.float32)
+    n = X.shape[0]
+    flat = X.reshape(n, -1)
+    plane_src = np.asarray(getattr(tables, "plane_src", tables))
+    salt = int(salt) & 0xFFFFFFFF
+    t = np.stack([tags(np.ascontiguousarray(flat[:, p])) for p in plane_src])        # [S][n]
+    keys = np.array([[mix64(int(v) ^ salt) for v in row] for row in t], dtype=np.uint64).reshape(len(plane_src), n)
+    g = np.argmin(keys, axis=0).astype(np.int32)                                      # (the first minimum: the lowest s)
+    return g, t[g, np.arange(n)]
+
+
+def canonical_planes(X, tables, salt):
+    """Every row of X as its class's canonical image X[plane_src[g]], in X's shape."""
+    X = np.ascontiguousarray(X, dtype=np.float32)
+    plane_src = np.asarray(getattr(tables, "plane_src", tables))
+    g, _ = canonical_elements(X, plane_src, salt)
+    return np.ascontiguousarray(np.take_along_axis(X.reshape(X.shape[0], -1), plane_src[g], axis=1)).reshape(X.shape)
+
+
+def canonical_forward(forward, X, tables, salt):
+    """The canonical forward from a plain one, in numpy, as pick_forward is the pick's: `forward`
+    applied to each row's canonical image, the policies read back through move_src[r][g].  What
+    gz_net_forward_sym_canon computes without a cache (and, the cache being exact, with one)."""
+    X = np.ascontiguousarray(X, dtype=np.float32)
+    move_src = [np.asarray(m) for m in tables.move_src]
+    g, _ = canonical_elements(X, tables, salt)
+    outs = forward(canonical_planes(X, tables, salt))
+    return [np.ascontiguousarray(np.take_along_axis(o, move_src[r][g], axis=1)) for r, o in enumerate(outs[:-1])] + [outs[-1]]
+
+
 def check_permutation(table, what):
     t = np.asarray(table)
     if t.ndim != 1 or not np.array_equal(np.sort(t), np.arange(len(t))):

@@ -401,6 +401,44 @@ int gz_net_forward_cached_device(gz_net* net, gz_eval_cache* cache, void* stream
  * would hit now; no claim, no copy, no flush.  For tests and diagnostics.  Synchronous. */
 int gz_eval_cache_probe(gz_eval_cache* cache, int device_ptr, const float* planes, int n, int* hit);
 
+/* ---- canonical orientation: symmetric positions share one forward and one cache entry -------------
+ * A third symmetry form beside the average and the pick.  Each row is evaluated under the ONE element
+ * g that maps it to its symmetry class's canonical image, and the policy is mapped back; a cache may
+ * stand in front of that forward.  With the pick's reading of a row (32-bit patterns), E, S, a 32-bit
+ * salt, and the cache's hashes (above; csrc/nn/symmetry.h states all of it as functions a CPU runs):
+ *   X_s[i] = X[plane_src[s][i]]                          image s, s in [0, S)
+ *   t_s = h2(X_s) << 32 | h1(X_s)                        the cache's 64-bit row tag of image s
+ *   k_s = mix64(t_s ^ uint64(salt))                      a bijection of the tag
+ *   g   = the s with the smallest (k_s, s)               ties, equal images included: the lowest s
+ *   X'  = X_g;  p', v' = the net's ordinary forward of X' (cache == NULL) or the cached forward of X';
+ *   out_r[m] = p'_r[move_src[r][g][m]];  values = v'
+ * 1. No floating-point operation is added: g depends on the row, the tables and the salt alone, and a
+ *    row is bit for bit the plain forward of X_g read through move_src[g] in any batch, chunk, entry
+ *    point or replay.  count = 1 with the identity is gz_net_forward.  Tables that are no group are
+ *    served; they get this and nothing more.
+ * 2. Where the tables are closed under composition (every game's are), a row and each of its images
+ *    get the same X': through a cache the second one hits, and if the row's S images are all distinct
+ *    out_X[r][m] == out_Y[r][move_src[r][t][m]] exactly for Y = X_t (the average gives that to 1e-6).
+ * 3. A row that is its own image under some element is evaluated correctly, under the lowest such s;
+ *    2's equality is not promised for it.  A tag collision between different images (2^-64 a pair)
+ *    can cost sharing, never correctness: the cache compares all plane words.
+ * sym_canon_expand_kernel (csrc/nn/symmetry.hip: one workgroup per row, the row in LDS, 2 S modular
+ * sums) and the pick's gather stand around one gz_net_forward_device, or one cached call, per chunk
+ * of 2,048 rows (GZ_SYM_CHUNK_ROWS lowers it) of canonical planes: at the defaults a call of n rows is
+ * util/evalcache.py's CacheModel.call(canonical planes) exactly, and the cache's flush rules hold
+ * unchanged.  Refusals, before any device call: the pick's ("symmetry: ..."), and with a cache the
+ * cache's ("eval cache: ...": made for another net or device).  A net in gz_net_set_output_logits
+ * mode is served.  Whether this plays or trains stronger is not measured here. */
+int gz_net_forward_sym_canon(gz_net* net, gz_symmetry* s, unsigned salt, gz_eval_cache* cache /* may be NULL */,
+                             const float* planes, int n, float* const* policies, float* values);
+/* On the caller's stream; with a cache it blocks once per chunk, as gz_net_forward_cached_device. */
+int gz_net_forward_sym_canon_device(gz_net* net, gz_symmetry* s, unsigned salt, gz_eval_cache* cache, void* stream,
+                                    const float* d_planes, int n, float* const* d_policies, float* d_values);
+/* g and (tag_out != NULL) t_g of each row of planes [n][plane_elems] (host memory, or device memory
+ * when device_ptr), as the GPU kernel computes them: for tests and diagnostics.  Synchronous. */
+int gz_symmetry_canon(gz_symmetry* s, unsigned salt, int device_ptr, const float* planes, int n, int* g_out,
+                      unsigned long long* tag_out /* may be NULL */);
+
 /* Diagnostics: with GZ_KERNEL_STAMPS set in the environment, gz_net_forward records per-workgroup
  * s_memtime stamps at phase boundaries; out8[0] = workgroups averaged, out8[1..4] = their mean
  * cycles of (input + initial conv, residual trunk, head 1x1 convs + features, fused dense heads)
@@ -488,6 +526,15 @@ long gz_runner_sym_pick_rows(gz_runner* r);
  * net.  The cache must outlive the runner.  Without this call the launcher issues exactly the calls it
  * always did. */
 int gz_runner_set_cache(gz_runner* r, gz_eval_cache* cache);
+/* Self-play in the canonical orientation (gz_net_forward_sym_canon, above), with or without a cache:
+ * gz_runner_set_symmetry's launch with sym_canon_expand_kernel in the pick expand's place, and with a
+ * cache gz_runner_set_cache's probe / forward of the misses / fill reading the canonical planes and
+ * writing the raw outputs the gather reads.  Output staging is forced on, and
+ * gz_runner_sym_pick_rows counts these rows.  Before gz_runner_start only.  Refused, before any
+ * device call: a started runner; a zero-copy runner; a runner that already has a symmetry, a cache or
+ * a canonical setting (and gz_runner_set_symmetry / gz_runner_set_cache on a runner in canonical
+ * mode); the pick's and the cache's refusals.  Both objects must outlive the runner. */
+int gz_runner_set_canonical(gz_runner* r, gz_symmetry* s, unsigned salt, gz_eval_cache* cache /* may be NULL */);
 int gz_runner_start(gz_runner* r);   /* once per runner: a stopped runner cannot be restarted */
 int gz_runner_wait_batches(gz_runner* r, long total_batches, double timeout_s);
 int gz_runner_wait_rows(gz_runner* r, long total_rows, double timeout_s);
