@@ -42,6 +42,8 @@
 
 #include <utility>
 
+#include "rowpair.h"
+
 namespace gznn {
 
 constexpr int kMaxRoles = 4;
@@ -194,7 +196,10 @@ __host__ __device__ constexpr int lcm_c(int a, int b) { return a / gcd_c(a, b) *
 // the 4-wave layout's co tiles, half its position tiles: half the B-fragment reads per MFMA, twice
 // the weight fragments); WG = 5: WG = 4's decomposition with ONE image per board, overwritten in place
 // (INPL), and a 2-stage weight ring, so a wave fits 256 registers and a workgroup half the LDS: two
-// independent workgroups per CU, whose epilogues, barriers and fixed phases overlap each other's MFMAs
+// independent workgroups per CU, whose epilogues, barriers and fixed phases overlap each other's MFMAs;
+// at four position tiles WG = 5 is the row-pair geometry (RP below, rowpair.h: 8 x 8 boards only) and
+// WG = 6 the same in-place kernel with a board per group, for the other boards of four tiles
+__host__ __device__ constexpr bool wg_in_place(int wg) { return wg == 5 || wg == 6; }
 template <int F, int PTN, int NB = 1, int P = 1, int WG = 1>
 struct Geo {
     static constexpr int P2 = P == 3 ? 2 : 1;        // bf16 parts per activation in the LDS image
@@ -203,8 +208,8 @@ struct Geo {
     static constexpr int NPOS = 16 * PTN;            // position capacity (the real count is kp.npos)
     static constexpr int PT = PTN;                   // position tiles per board (MFMA N)
     static constexpr int TT = NB * PT;               // position tiles per wave (all boards)
-    static constexpr int NWV = WG == 3 ? 8 : (WG == 4 || WG == 5) ? 2 : 4;   // waves per group
-    static constexpr int NGR = WG == 2 || WG == 4 || WG == 5 ? 2 : 1;      // wave groups per workgroup
+    static constexpr int NWV = WG == 3 ? 8 : (WG == 4 || wg_in_place(WG)) ? 2 : 4;   // waves per group
+    static constexpr int NGR = WG == 2 || WG == 4 || wg_in_place(WG) ? 2 : 1;      // wave groups per workgroup
     static constexpr int CT = F / (16 * NWV);        // co tiles per wave (MFMA M)
     static constexpr int KC = F / 32;                // k-steps per tap
     static constexpr int CPR = F / 8;                // 16-byte chunks of channels per row
@@ -242,8 +247,8 @@ struct Geo {
     // ring depth; the two-board split kernels take exactly one tap's stages (R = KC / KS) so the
     // looped conv's body is one tap (a deeper ring made the body three taps and spilled)
     // (WG = 5: 256 registers per wave -- the 64-VGPR 2-stage ring of ring_depth below)
-    static constexpr int R0 = (P2 == 2 && (NB == 2 || WG == 2 || WG == 4 || WG == 5) && (KC / KS) >= 3 && NST % (KC / KS) == 0 &&
-                               (KC / KS) * KS * NFR * 4 <= (WG == 4 ? GZ_H2_RING_VGPRS : WG == 5 ? 64 : 96))
+    static constexpr int R0 = (P2 == 2 && (NB == 2 || WG == 2 || WG == 4 || wg_in_place(WG)) && (KC / KS) >= 3 && NST % (KC / KS) == 0 &&
+                               (KC / KS) * KS * NFR * 4 <= (WG == 4 ? GZ_H2_RING_VGPRS : wg_in_place(WG) ? 64 : 96))
                                   ? KC / KS
                                   : ring_depth(NST, KS, NFR, CT >= 4 ? 64 : 96);
     // Single-image mode: when two ping-pong images (+ bias table) do not fit the 160 KB of LDS
@@ -270,7 +275,16 @@ struct Geo {
     // own -- each conv reads image X and its epilogue, behind a workgroup barrier, writes X; staging and
     // head scratch alias the group's image.  The looped conv, the chains, the select stores, the wave
     // groups and the fused heads stay those of the two-image kernels (SI is false).
-    static constexpr bool INPL = WG == 5;
+    static constexpr bool INPL = wg_in_place(WG);
+    // Row pairs (rowpair.h): a position tile is one board row of each of the workgroup's two boards,
+    // wave group g the tile set g of both (rows 0-3 / rows 7-4), so that tile 0 of a set lies wholly off
+    // the board under three taps, whose MFMAs and B reads the looped conv leaves out.  The two images
+    // lie IMG_STRIDE apart (a multiple of 256 bytes: rowpair_tap_offset).  H = W = 8 only.
+    static constexpr bool RP = WG == 5 && PTN == kRowPairTiles;
+    static constexpr int IMG_STRIDE = ACT_BYTES + (RP ? kRowPairPad : 0);   // a wave group's image from the previous one's
+    static_assert(!RP || (ROWS == kRowPairRowBytes && HALF == kRowPairHalf && ACT_BYTES == kRowPairImage && ZROWS == 2 &&
+                          IMG_STRIDE == kRowPairStride && NPOS == kRowPairSide * kRowPairSide),
+                  "row pairs: rowpair.h's image");
     // Global residual: when the fp32 residual stream (+ the accumulators) would need more than 256
     // VGPRs (F = 256 on 13x13: 2 x 176), it lives in a per-workgroup device scratch instead of
     // registers, lane-contiguous (one coalesced 1 KB store / load per wave and tile).
@@ -279,10 +293,10 @@ struct Geo {
     // accumulators + residual) the register allocator moves values between VGPRs and AGPRs, and a
     // copy of an inline-asm load's destination could be taken before the data lands; such kernels
     // (and the single-image ones) issue the ring with ordinary loads, which the compiler waits for.
-    static constexpr bool TRACKED = SI || LIVE_VGPRS > 300 || (P2 == 2 && (NB == 2 || WG == 2 || WG == 4 || WG == 5));
+    static constexpr bool TRACKED = SI || LIVE_VGPRS > 300 || (P2 == 2 && (NB == 2 || WG == 2 || WG == 4 || wg_in_place(WG)));
     static_assert(F % 64 == 0, "filters must be a multiple of 64");
     static_assert(!SI || NB == 1, "single-image mode takes one board per workgroup");
-    static_assert(WG == 1 || ((WG == 2 || WG == 4 || WG == 5) && NB == 1 && !SI) || (WG == 3 && !SI && CT >= 1),
+    static_assert(WG == 1 || ((WG == 2 || WG == 4 || wg_in_place(WG)) && NB == 1 && !SI) || (WG == 3 && !SI && CT >= 1),
                   "wave groups: two images, or one in place (INPL), never the single-image conv and heads");
     static_assert(!INPL || (P == 3 && WRAP), "in place: the split F = 128 kernels");
     static_assert(!RG || SI, "the global residual is implemented for single-image kernels");
@@ -494,9 +508,16 @@ __device__ __forceinline__ void launder_ptr(T*& p) { asm volatile("" : "+v"(p));
 struct TapAddr {
     int row, rot;
 };
-template <int F, int PTN, int P = 1>
-__device__ __forceinline__ TapAddr tap_base(int tap, int pt, int lane, const Board& bd) {
+// RP: row pairs (rowpair.h), tile set rset (wave-uniform) -- the offset counts from board 0's image and
+// holds the lane's board; no tap masks
+template <int F, int PTN, int P = 1, bool RP = false>
+__device__ __forceinline__ TapAddr tap_base(int tap, int pt, int lane, const Board& bd, int rset = 0) {
     using G = Geo<F, PTN, 1, P>;
+    if constexpr (RP) {
+        using GR = Geo<F, PTN, 1, P, 5>;
+        static_assert(GR::RP && G::WRAP, "row pairs: the in-place split kernel at four tiles");
+        return TapAddr{rowpair_tap_offset<G::ROWS, GR::IMG_STRIDE>(rset, pt, lane, tap), 0};
+    }
     const int li = lane & 15, g = lane >> 4;
     const int dy = tap / 3 - 1, dx = tap % 3 - 1;
     const int p = 16 * pt + li;
@@ -701,15 +722,22 @@ __device__ __forceinline__ void tile_leave(f32x4 (&acc)[CT][TT], int t) {
     for (int ct = 0; ct < CT; ++ct) asm volatile("" : "+a"(acc[ct][t]));
 }
 
+// Row pairs (Geo::RP, tile set rset): under a tap that leaves tile 0 off the board (skip0, wave-uniform)
+// a uniform branch per k-step goes round tile 0's chains and its B reads; the rest of the body is the
+// same straight line for every tap.  Where the iteration's last k-step reads ahead into the next tap,
+// tile 0 is read only if that tap has it (rd0): an absent tile is not read, a returning one is read a
+// k-step before its chains, as every tile is.
 template <int F, int PTN, int NB, int P, int WG, int PASS, int ST, bool EPI = false, class Epi = NoEpi>
 __device__ __forceinline__ void conv_stage_l(const char* __restrict__ X, Ring<F, PTN, NB, P, WG>& ring,
                                              f32x4 (&acc)[Geo<F, PTN, NB, P, WG>::CT][Geo<F, PTN, NB, P, WG>::TT],
                                              bf16x8 (&b)[Geo<F, PTN, NB, P, WG>::TT][Geo<F, PTN, NB, P, WG>::P2],
                                              const __bf16* wres, uint32_t woff, int gs_it, int gmax, int& lane,
-                                             const Board& bd, int tap0, bool last_it, const Epi& epi = Epi{}) {
+                                             const Board& bd, int tap0, bool last_it, const Epi& epi, int rset, bool skip0,
+                                             bool rd0, int (&tb)[Geo<F, PTN, NB, P, WG>::PT]) {
     using G = Geo<F, PTN, NB, P, WG>;
     constexpr int R = G::R, KS = G::KS, CT = G::CT, PT = G::PT, KC = G::KC, P2 = G::P2, WP = G::WP;
     static_assert(P != 2 || G::TRACKED, "two-pass split: compiler-tracked weight loads");
+    static_assert(!G::RP || (G::TPI == 1 && !EPI && NB == 1), "row pairs: one tap per iteration");
     static_assert(G::U % R == 0, "ring slots must be static within an iteration");
     if constexpr (P == 2) {
         constexpr int SLOT = (ST + R - 1) % R;
@@ -736,13 +764,29 @@ __device__ __forceinline__ void conv_stage_l(const char* __restrict__ X, Ring<F,
         const int tap = tap0 + jn / KC, kc = jn % KC;   // and its tap
         if (kc == 0) launder(lane);
         int nb_off[PT];
+        if constexpr (G::RP) {
+            // a tap's four tile offsets are formed once, when the read ahead enters the tap, and kept
+            // (laundered, so that its k-steps differ by the reads' immediate offsets)
+            if (kc == 0) {
 #pragma unroll
-        for (int pt = 0; pt < PT; ++pt) nb_off[pt] = tap_offset<F, PTN, P>(tap_base<F, PTN, P>(tap, pt, lane, bd), kc);
+                for (int pt = 0; pt < PT; ++pt) {
+                    if (pt == 0 && !rd0) continue;    // (absent under the next tap: no address either)
+                    tb[pt] = tap_base<F, PTN, P, true>(tap, pt, lane, bd, rset).row;
+                    launder(tb[pt]);
+                }
+            }
+#pragma unroll
+            for (int pt = 0; pt < PT; ++pt) nb_off[pt] = tb[pt] + 64 * kc;
+        } else {
+#pragma unroll
+            for (int pt = 0; pt < PT; ++pt) nb_off[pt] = tap_offset<F, PTN, P>(tap_base<F, PTN, P>(tap, pt, lane, bd), kc);
+        }
 #pragma unroll
         for (int bb = 0; bb < NB; ++bb)
 #pragma unroll
             for (int pt = 0; pt < PT; ++pt) {
                 const int t = bb * PT + pt;
+                if (!(G::RP && t == 0) || !skip0)
 #pragma unroll
                 for (int ct = 0; ct < CT; ++ct) {
                     const bf16x8 w_hi = ring.r[ST % R][k][ct * WP];
@@ -759,8 +803,11 @@ __device__ __forceinline__ void conv_stage_l(const char* __restrict__ X, Ring<F,
                 {   // tile t of the next k-step (unconditional: past the conv's last k-step the tap
                     // index is 9, whose mask bit is clear, so the reads hit the zero area)
                     const char* a = X + nb_off[pt] + bb * G::ACT_BYTES;
+                    // (row pairs, tile 0: within a tap as the tap has it, into the next tap as rd0 says)
+                    if (!(G::RP && t == 0) || (kc != 0 ? !skip0 : rd0)) {
 #pragma unroll
-                    for (int h = 0; h < P2; ++h) b[t][h] = *(const bf16x8*)(a + h * G::HALF);
+                        for (int h = 0; h < P2; ++h) b[t][h] = *(const bf16x8*)(a + h * G::HALF);
+                    }
                 }
                 if constexpr (P2 == 1) {   // (the asm chains are not MFMAs to the scheduler)
                     __builtin_amdgcn_sched_group_barrier(0x008, CT * (P == 2 && PASS == 0 ? 2 : 1), 0);   // MFMA
@@ -788,10 +835,10 @@ __device__ __forceinline__ void conv_iter(const char* __restrict__ X, Ring<F, PT
                                           f32x4 (&acc)[Geo<F, PTN, NB, P, WG>::CT][Geo<F, PTN, NB, P, WG>::TT],
                                           bf16x8 (&b)[Geo<F, PTN, NB, P, WG>::TT][Geo<F, PTN, NB, P, WG>::P2],
                                           const __bf16* wres, uint32_t woff, int gs_it, int gmax, int& lane,
-                                          const Board& bd, int tap0, bool last_it, const Epi& epi,
-                                          std::integer_sequence<int, ST...>) {
+                                          const Board& bd, int tap0, bool last_it, const Epi& epi, int rset, bool skip0,
+                                          bool rd0, int (&tb)[Geo<F, PTN, NB, P, WG>::PT], std::integer_sequence<int, ST...>) {
     (conv_stage_l<F, PTN, NB, P, WG, PASS, ST, EPI, Epi>(X, ring, acc, b, wres, woff, gs_it, gmax, lane, bd, tap0, last_it,
-                                                         epi), ...);
+                                                         epi, rset, skip0, rd0, tb), ...);
 }
 
 // PASS (P = 2): 0 starts the accumulators, 1 adds to them.  EPI: the epilogue epi(t) of every
@@ -800,7 +847,7 @@ template <int F, int PTN, int NB, int P, int WG = 1, int PASS = 0, bool EPI = fa
 __device__ __forceinline__ void conv3x3_looped(const char* __restrict__ X, Ring<F, PTN, NB, P, WG>& ring,
                                                f32x4 (&acc)[Geo<F, PTN, NB, P, WG>::CT][Geo<F, PTN, NB, P, WG>::TT],
                                                const __bf16* wres, uint32_t woff, int gs0, int gmax, int lane,
-                                               const Board& bd, const Epi& epi = Epi{}) {
+                                               const Board& bd, const Epi& epi = Epi{}, int rset = 0) {
     using G = Geo<F, PTN, NB, P, WG>;
     constexpr int PT = G::PT, TT = G::TT;
     if constexpr (PASS == 0) {
@@ -810,26 +857,57 @@ __device__ __forceinline__ void conv3x3_looped(const char* __restrict__ X, Ring<
             for (int t = 0; t < TT; ++t) acc[ct][t] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     bf16x8 b[TT][G::P2];
+    int tb[PT];    // row pairs: the current tap's tile offsets (conv_stage_l)
     launder(lane);
+    if constexpr (G::RP) {
+        // One tap per iteration, in tap order: set 0 goes round tile 0 under taps 0-2, set 1 under taps
+        // 6-8 (rowpair_skip)
+        static_assert(G::TPI == 1 && G::NIT == 9 && !EPI && NB == 1, "row pairs: one tap per iteration");
 #pragma unroll
-    for (int pt = 0; pt < PT; ++pt) {
-        const char* a = X + tap_offset<F, PTN, P>(tap_base<F, PTN, P>(0, pt, lane, bd), 0);
+        for (int pt = 0; pt < PT; ++pt) {   // tap 0, k-step 0 (set 0: without tile 0)
+            tb[pt] = tap_base<F, PTN, P, true>(0, pt, lane, bd, rset).row;
+            launder(tb[pt]);
+            const char* a = X + tb[pt];
+            if (pt != 0 || !rowpair_skip(rset, 0, 0)) {
 #pragma unroll
-        for (int bb = 0; bb < NB; ++bb)
-#pragma unroll
-            for (int h = 0; h < G::P2; ++h) b[bb * PT + pt][h] = *(const bf16x8*)(a + bb * G::ACT_BYTES + h * G::HALF);
-    }
-    if constexpr (G::P2 == 2) split_chain_enter(acc);
-    constexpr int NLOOP = EPI ? G::NIT - 1 : G::NIT;
+                for (int h = 0; h < G::P2; ++h) b[pt][h] = *(const bf16x8*)(a + h * G::HALF);
+            }
+        }
+        split_chain_enter(acc);
+        // (the set's three short taps start at tap first_short: rowpair_skip as one unsigned compare)
+        static_assert(rowpair_skip(0, 0, 0) && rowpair_skip(0, 0, 2) && !rowpair_skip(0, 0, 3) && !rowpair_skip(1, 0, 5) &&
+                      rowpair_skip(1, 0, 6) && rowpair_skip(1, 0, 8) && !rowpair_skip(1, 0, 9), "the short taps");
+        const int first_short = rset == 0 ? 0 : 6;
 #pragma clang loop unroll(disable)
-    for (int it = 0; it < NLOOP; ++it)
-        conv_iter<F, PTN, NB, P, WG, PASS, false, NoEpi>(X, ring, acc, b, wres, woff, gs0 + it * G::U, gmax, lane, bd,
-                                                       it * G::TPI, it == G::NIT - 1, NoEpi{},
-                                                       std::make_integer_sequence<int, G::U>{});
-    if constexpr (EPI)
-        conv_iter<F, PTN, NB, P, WG, PASS, true, Epi>(X, ring, acc, b, wres, woff, gs0 + NLOOP * G::U, gmax, lane, bd,
-                                                   NLOOP * G::TPI, true, epi, std::make_integer_sequence<int, G::U>{});
-    if constexpr (G::P2 == 2) split_chain_leave(acc);
+        for (int it = 0; it < G::NIT; ++it)
+            conv_iter<F, PTN, NB, P, WG, PASS, false, NoEpi>(X, ring, acc, b, wres, woff, gs0 + it * G::U, gmax, lane, bd, it,
+                                                             it == G::NIT - 1, NoEpi{}, rset,
+                                                             (unsigned)(it - first_short) < 3u,
+                                                             !((unsigned)(it + 1 - first_short) < 3u), tb,
+                                                             std::make_integer_sequence<int, G::U>{});
+        split_chain_leave(acc);
+    } else {
+#pragma unroll
+        for (int pt = 0; pt < PT; ++pt) {
+            const char* a = X + tap_offset<F, PTN, P>(tap_base<F, PTN, P>(0, pt, lane, bd), 0);
+#pragma unroll
+            for (int bb = 0; bb < NB; ++bb)
+#pragma unroll
+                for (int h = 0; h < G::P2; ++h) b[bb * PT + pt][h] = *(const bf16x8*)(a + bb * G::ACT_BYTES + h * G::HALF);
+        }
+        if constexpr (G::P2 == 2) split_chain_enter(acc);
+        constexpr int NLOOP = EPI ? G::NIT - 1 : G::NIT;
+#pragma clang loop unroll(disable)
+        for (int it = 0; it < NLOOP; ++it)
+            conv_iter<F, PTN, NB, P, WG, PASS, false, NoEpi>(X, ring, acc, b, wres, woff, gs0 + it * G::U, gmax, lane, bd,
+                                                             it * G::TPI, it == G::NIT - 1, NoEpi{}, 0, false, true, tb,
+                                                             std::make_integer_sequence<int, G::U>{});
+        if constexpr (EPI)
+            conv_iter<F, PTN, NB, P, WG, PASS, true, Epi>(X, ring, acc, b, wres, woff, gs0 + NLOOP * G::U, gmax, lane, bd,
+                                                          NLOOP * G::TPI, true, epi, 0, false, true, tb,
+                                                          std::make_integer_sequence<int, G::U>{});
+        if constexpr (G::P2 == 2) split_chain_leave(acc);
+    }
 }
 
 // Per-board channel sums over the board's positions of the wave's accumulator tiles: lane group g
@@ -1022,11 +1100,17 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
     constexpr int IP2 = G::WP;    // bf16 parts of the initial conv's operands (im2col scratch, w0 / w0lo)
     constexpr int PT = G::PT, TT = G::TT, CT = G::CT, R = G::R, NWV = G::NWV, NGR = G::NGR, kThreads = 64 * NWV;
     const int NPOS = kp.npos, H = kp.H, W = kp.W;     // the board (NPOS <= G::NPOS)
+    // wave group grp (WG = 2: threads 256 grp .. 256 grp + 255) takes boards NB grp .. of the
+    // workgroup; LDS: image set 0 [WG][NB][ACT], image set 1 [WG][NB][ACT], bias table
+    // (row pairs: group g stages, and sums the head features of, board g; from the initial conv to the
+    // heads' 1x1 convs its waves hold tile set g of both boards)
+    const int grp = NGR == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kThreads));
     Board bd{H, W, NPOS, kp.wmagic, {}};
     {
         const int li = threadIdx.x & 15;
 #pragma unroll
         for (int pt = 0; pt < PT; ++pt) {
+            if constexpr (G::RP) continue;   // (row pairs: rowpair_tap_offset tests the column itself)
             const int p = 16 * pt + li;
             const int r = bd.row(p), x = p - r * W;
             int m = 0;
@@ -1042,10 +1126,7 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
 
     constexpr bool SI = G::SI, RG = G::RG;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // wave group grp (WG = 2: threads 256 grp .. 256 grp + 255) takes boards NB grp .. of the
-    // workgroup; LDS: image set 0 [WG][NB][ACT], image set 1 [WG][NB][ACT], bias table
-    const int grp = NGR == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kThreads));
-    char* X0 = smem + grp * NB * ACT;                                  // [NB][ACT]
+    char* X0 = smem + grp * NB * G::IMG_STRIDE;                        // [NB][ACT]
     // (in place: X1 is X0, the group's one image; group 0's scratch is the workgroup's first image)
     constexpr bool INPL = G::INPL;
     char* X1 = SI ? smem : INPL ? X0 : smem + NGR * NB * ACT + grp * NB * ACT;      // [NB][ACT]
@@ -1062,6 +1143,24 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, li = lane & 15;
     const int co_base = wave * (F / NWV);
+    // Column li of the wave's tile t: the image it belongs to (Xg: the group's image set) and its
+    // position.  Row pairs: a tile holds a row of each of the workgroup's boards (rowpair_map), whatever
+    // the group; both terms are formed where they are used, from the li handed in.
+    auto tile_img = [&](char* Xg, int t, int li_) -> char* {
+        if constexpr (G::RP) return smem + (li_ >> 3) * G::IMG_STRIDE;
+        else return Xg + (t / PT) * ACT;
+    };
+    auto tile_pos = [&](int t, int li_) -> int {
+        if constexpr (G::RP) return rowpair_map(grp, t, li_).pos;
+        else return 16 * (t % PT) + li_;
+    };
+    // (row pairs: a tile's row is not a constant, so its store address is a register of its own; each
+    // epilogue forms them from a laundered li instead of keeping -- spilling -- them across the convs)
+    auto li_now = [&]() -> int {
+        int v = li;
+        if constexpr (G::RP) launder(v);
+        return v;
+    };
     const int C = kp.C, K0 = kp.K0;
 
     // The NB boards' input planes, fetched before anything else with 16-byte loads so that one round
@@ -1228,9 +1327,10 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
             if (s + 1 < nk0) load_w0(s + 1, an, alon);
 #pragma unroll
             for (int pt = 0; pt < PT; ++pt) {
-                const int p = 16 * pt + li;
+                const int p = tile_pos(pt, li);
                 const int q = p < NPOS ? p : NPOS;
-                const int o = q * imrow + ((((s * 4 + g)) ^ (q & imswz)) << 4);
+                // (row pairs: the im2col rows of the lane's board, staged by that board's group)
+                const int o = q * imrow + ((((s * 4 + g)) ^ (q & imswz)) << 4) + (G::RP ? ((li >> 3) - grp) * G::IMG_STRIDE : 0);
                 const bf16x8 bq = *(const bf16x8*)(IM + o);
 #pragma unroll
                 for (int ct = 0; ct < CT; ++ct) {
@@ -1295,7 +1395,8 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
                     }
                 }
             }
-        } else
+        } else {
+        const int lie = li_now();
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
             const int co = co_base + 16 * ct + 4 * g;
@@ -1323,9 +1424,11 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
                     store_act<F, PTN, 1, false>(X0 + bb * ACT, 16 * pt + li, co, sv, NPOS);
                     store_lo_scratch<F, PTN>(xlo, 16 * pt + li, co, sv, NPOS);
                 } else {
-                    store_act<F, PTN, P, !G::SI>(X0 + bb * ACT, 16 * pt + li, co, preact ? pre_act(v, psc, psh, kp.leaky) : v, NPOS);
+                    store_act<F, PTN, P, !G::SI>(tile_img(X0, bb * PT + pt, lie), tile_pos(pt, lie), co,
+                                                 preact ? pre_act(v, psc, psh, kp.leaky) : v, NPOS);
                 }
             }
+        }
         }
         if constexpr (V2)
             if (kp.cal) cal_partial(0, bb, li, g);   // layer 0: the initial conv block's output
@@ -1468,6 +1571,7 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
         const float* b_b = b_a + F;
 
         static_assert(!(INPL && kEpiInConv), "an epilogue inside the conv writes the other image");
+        static_assert(!(G::RP && (V2 || !G::LOOP)), "row pairs: the v1 looped conv");
         if constexpr (!V2 && G::LOOP && kEpiInConv) {
             // the same two epilogues as below, run per position tile inside each conv's last k-step
             float4 bia[CT];
@@ -1507,9 +1611,11 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
             __syncthreads();
             continue;
         }
-        if constexpr (G::LOOP) conv3x3_looped<F, PTN, NB, P, WG>(X0, ring, acc, kp.wres, woff, (2 * blk) * G::NST, gmax, lane, bd);
+        // (row pairs: the B-fragment offsets count from board 0's image, tap_base)
+        if constexpr (G::LOOP) conv3x3_looped<F, PTN, NB, P, WG>(G::RP ? smem : X0, ring, acc, kp.wres, woff, (2 * blk) * G::NST, gmax, lane, bd, NoEpi{}, grp);
         else conv3x3<F, PTN, NB, P, WG>(X0, ring, acc, kp.wres, woff, (2 * blk) * G::NST, gmax, lane, bd);
         if constexpr (INPL) __syncthreads();    // in place: every wave's last read of the image, then its stores
+        const int lia = li_now();
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
             const int co = co_base + 16 * ct + 4 * g;
@@ -1521,12 +1627,12 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
                 v[1] = act_mx(v[1] + bias.y, alpha);
                 v[2] = act_mx(v[2] + bias.z, alpha);
                 v[3] = act_mx(v[3] + bias.w, alpha);
-                store_act<F, PTN, P, !G::SI>(X1 + (t / PT) * ACT, 16 * (t % PT) + li, co, v, NPOS);
+                store_act<F, PTN, P, !G::SI>(tile_img(X1, t, lia), tile_pos(t, lia), co, v, NPOS);
             }
         }
         __syncthreads();
 
-        if constexpr (G::LOOP) conv3x3_looped<F, PTN, NB, P, WG>(X1, ring, acc, kp.wres, woff, (2 * blk + 1) * G::NST, gmax, lane, bd);
+        if constexpr (G::LOOP) conv3x3_looped<F, PTN, NB, P, WG>(G::RP ? smem : X1, ring, acc, kp.wres, woff, (2 * blk + 1) * G::NST, gmax, lane, bd, NoEpi{}, grp);
         else conv3x3<F, PTN, NB, P, WG>(X1, ring, acc, kp.wres, woff, (2 * blk + 1) * G::NST, gmax, lane, bd);
         if constexpr (INPL) __syncthreads();
         if constexpr (V2) {   // s += SE(conv2 + bias); image = act(BN_1 of the next block (s)), model.py:128-149
@@ -1565,6 +1671,7 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
             if (kp.cal) cal_reduce(blk + 1);
             continue;
         }
+        const int lib = li_now();
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
             const int co = co_base + 16 * ct + 4 * g;
@@ -1579,7 +1686,7 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
                 v[3] = act_mx(v[3] + bias.w + r[3], alpha);
                 resid[ct][t] = v;
                 acc[ct][t] = v;
-                store_act<F, PTN, P, !G::SI>(X0 + (t / PT) * ACT, 16 * (t % PT) + li, co, v, NPOS);
+                store_act<F, PTN, P, !G::SI>(tile_img(X0, t, lib), tile_pos(t, lib), co, v, NPOS);
             }
         }
         __syncthreads();
@@ -1611,7 +1718,7 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
     // (v2 single-image kernels: the lane's position and channel-group terms re-formed here, so the
     // heads' per-tile addresses are not computed ahead of the tower and kept -- spilled -- across it)
     int lih = li, gh = g;
-    if constexpr (V2 && SI) {
+    if constexpr ((V2 && SI) || G::RP) {
         launder(lih);
         launder(gh);
     }
@@ -1654,7 +1761,9 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
 #pragma unroll
     for (int bb = 0; bb < NB; ++bb) {
         const int board = board0 + bb;
-        if (kp.gapF && board < kp.n) {   // pooling value head: the trunk's channel means (model.py:263)
+        // (row pairs: a board's positions lie in both groups' waves, so this sum's order cannot be kept --
+        // the host gives nets with a pooling value head the kernel with a board per group)
+        if (!G::RP && kp.gapF && board < kp.n) {   // pooling value head: the trunk's channel means (model.py:263)
             const float inv = 1.f / (float)NPOS;
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {
@@ -1667,10 +1776,13 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
             }
         }
         // one 1x1 head conv (output h) of board bb from the fp32 stream, weights wv
+        // (row pairs: the lane's board's partials, in that board's image)
         auto head_conv = [&](int h, const float4 (&wv)[CT]) {
+            float* hp = hpart;
+            if constexpr (G::RP) hp = (float*)tile_img(SCR, 0, lih);
 #pragma unroll
             for (int pt = 0; pt < PT; ++pt) {
-                const int p = 16 * pt + lih;
+                const int p = tile_pos(pt, lih);
 #pragma unroll
                 for (int ct = 0; ct < CT; ++ct) {
                     const f32x4 a = acc[ct][bb * PT + pt];
@@ -1680,7 +1792,7 @@ __device__ __forceinline__ void trunk_body(const KParams& kp) {
                     s += a[3] * wv[ct].w;
                     s += __shfl_xor(s, 16, 64);
                     s += __shfl_xor(s, 32, 64);
-                    if (gh == 0 && p < NPOS) hpart[((bb * NT16 + co_base / 16 + ct) * HC + h) * NPOS + p] = s;
+                    if (gh == 0 && p < NPOS) hp[((bb * NT16 + co_base / 16 + ct) * HC + h) * NPOS + p] = s;
                 }
             }
         };
@@ -1772,6 +1884,14 @@ template <int F, int PTN, int P>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
 trunk_kernel_h2i(const KParams kp) {
     trunk_body<F, PTN, 1, 2, P, false, 5>(kp);
+}
+// At four position tiles trunk_kernel_h2i is the row-pair kernel (Geo::RP, rowpair.h), which takes 8 x 8
+// boards without a pooling value head only.  The other boards of four tiles (7 x 7, 7 x 8, 8 x 7) run
+// the same in-place kernel with a board per group, as the smaller boards do, under this name.
+template <int F, int PTN, int P>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
+trunk_kernel_h2ig(const KParams kp) {
+    trunk_body<F, PTN, 1, 2, P, false, 6>(kp);
 }
 
 template <int F, int PTN, int NB, int WPE, int P>

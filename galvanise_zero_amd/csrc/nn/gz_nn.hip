@@ -157,11 +157,17 @@ extern "C" const char* gz_nn_last_error(void) { return g_err.c_str(); }
 // up to 8 residual blocks) and the runtime reports two resident workgroups; otherwise 23 stays.
 constexpr int kSmallVariant = 11, kLargeVariant = 23, kLargeFallback = 21, kLargeMinRows = 257;
 constexpr int kLargeInPlace = 25;
+// At four position tiles variant 25 is the row-pair kernel (rowpair.h), for 8 x 8 boards without a
+// pooling value head; the other such boards get the same in-place kernel with a board per group.
+constexpr int kInPlaceGeneric = 26;
 constexpr int kCUs = 256;
 
-static KernelChoice select_kernel(int fpad, int pt, int v, int precision, bool v2) {
+static KernelChoice select_kernel(const gz_net_desc& d, int fpad, int pt, int v, int precision, bool v2) {
     if (pt < 1 || pt > kMaxPT) return KernelChoice{};
-    return trunk_variant(fpad, pt, v, precision, v2);
+    KernelChoice k = trunk_variant(fpad, pt, v, precision, v2);
+    if (k.fn && k.square8 && (d.input_columns != 8 || d.input_rows != 8 || gap_features(d)))
+        k = trunk_variant(fpad, pt, kInPlaceGeneric, precision, v2);
+    return k;
 }
 
 // gz_net_create's first half: every refusal that needs no device, and the net's host-side state.
@@ -207,9 +213,9 @@ static gz_net* create_host(const gz_net_desc& d, int device, gz_net::Trunk* in_p
         }
         min_large = 1 << 30;   // one conv kernel for every launch size
     }
-    KernelChoice kc = layerwise ? KernelChoice{} : select_kernel(fpad, pt, vs, precision, v2);
-    KernelChoice kl = layerwise ? KernelChoice{} : select_kernel(fpad, pt, vl, precision, v2);
-    if (!kl.fn && vl == kLargeVariant) kl = select_kernel(fpad, pt, kLargeFallback, precision, v2);
+    KernelChoice kc = layerwise ? KernelChoice{} : select_kernel(d, fpad, pt, vs, precision, v2);
+    KernelChoice kl = layerwise ? KernelChoice{} : select_kernel(d, fpad, pt, vl, precision, v2);
+    if (!kl.fn && vl == kLargeVariant) kl = select_kernel(d, fpad, pt, kLargeFallback, precision, v2);
     // wave-group kernels: each group's staging / heads scratch must fit its own image
     auto wg_fits = [&](const KernelChoice& c) {
         if (c.groups == 1) return true;
@@ -224,13 +230,13 @@ static gz_net* create_host(const gz_net_desc& d, int device, gz_net::Trunk* in_p
     if (kl.fn && !wg_fits(kl)) {
         // the wave-group default (23) does not fit this geometry's scratch: the two-board 4-wave
         // kernel (21, one image per workgroup) before the one-board one
-        kl = vl == kLargeVariant ? select_kernel(fpad, pt, kLargeFallback, precision, v2) : KernelChoice{};
+        kl = vl == kLargeVariant ? select_kernel(d, fpad, pt, kLargeFallback, precision, v2) : KernelChoice{};
         if (kl.fn && !wg_fits(kl)) kl = KernelChoice{};
     }
     if (kc.fn && !wg_fits(kc)) kc = KernelChoice{};
     // the two-workgroups-per-CU candidate for the large launches (decided below, with the device)
     KernelChoice ki = !layerwise && getenv("GZ_KERNEL_VARIANT") == nullptr && kl.fn
-                          ? select_kernel(fpad, pt, kLargeInPlace, precision, v2) : KernelChoice{};
+                          ? select_kernel(d, fpad, pt, kLargeInPlace, precision, v2) : KernelChoice{};
     if (ki.fn && !wg_fits(ki)) ki = KernelChoice{};
     if (kc.fn && !kl.fn && vl != vs) {   // geometries with a single (one board per workgroup) variant
         kl = kc;
@@ -279,7 +285,7 @@ static gz_net* create_host(const gz_net_desc& d, int device, gz_net::Trunk* in_p
                                       : scr_in;
         // (in place: the scratch lies inside the images, wg_fits)
         t.btab_off = c.single_image ? align16(std::max(c.act_bytes, scr))
-                     : c.in_place   ? c.nb * c.act_bytes
+                     : c.in_place   ? c.nb * c.act_bytes + c.img_pad
                                     : c.nb * c.act_bytes + std::max(c.nb * c.act_bytes, scr);
         t.resid_bytes = c.resid_bytes;
         t.smem = t.btab_off + bias_table_bytes(fpad, d.residual_layers);

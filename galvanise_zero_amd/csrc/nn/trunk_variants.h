@@ -26,6 +26,8 @@ struct KernelChoice {
     int groups = 1;                // wave groups (2: trunk_kernel8, a board per group)
     bool in_place = false;         // one image per board, overwritten in place, with the two-image kernels' heads
     int wgs_per_cu = 1;            // workgroups per CU the kernel is built for (registers and LDS)
+    int img_pad = 0;               // in place: bytes between the two boards' images (row pairs: 160)
+    bool square8 = false;          // row pairs: 8 x 8 boards without a pooling value head only
     char name[64] = {0};           // the kernel as rocprofv3 names it
 };
 
@@ -89,7 +91,24 @@ KernelChoice kernelh2i_for() {
     k.groups = 2;
     k.in_place = true;
     k.wgs_per_cu = 2;
+    k.img_pad = Geo<F, PTN, 1, P, 5>::IMG_STRIDE - Geo<F, PTN, 1, P, 5>::ACT_BYTES;
+    k.square8 = Geo<F, PTN, 1, P, 5>::RP;
     std::snprintf(k.name, sizeof(k.name), "gznn::trunk_kernel_h2i<%d, %d, %d>", F, PTN, P);
+    return k;
+}
+
+// variant 25 for the boards of four position tiles that trunk_kernel_h2i's row pairs do not take
+// (variant 26 by number)
+template <int F, int PTN, int P>
+KernelChoice kernelh2ig_for() {
+    KernelChoice k;
+    k.fn = (const void*)&trunk_kernel_h2ig<F, PTN, P>;
+    k.act_bytes = Geo<F, PTN, 1, P, 6>::ACT_BYTES;
+    k.nb = 2;
+    k.groups = 2;
+    k.in_place = true;
+    k.wgs_per_cu = 2;
+    std::snprintf(k.name, sizeof(k.name), "gznn::trunk_kernel_h2ig<%d, %d, %d>", F, PTN, P);
     return k;
 }
 
@@ -129,6 +148,9 @@ KernelChoice variants(int v, int precision) {
                             if (v == 24) return kernelw8_for<F, PTN, 3>();
                             if (v == 23) return kernelh2_for<F, PTN, 3>();
                             if (v == 25) return kernelh2i_for<F, PTN, 3>();
+                            if constexpr (Geo<F, PTN, 1, 3, 5>::RP) {
+                                if (v == 26) return kernelh2ig_for<F, PTN, 3>();
+                            }
                         }
                     }
                 }
