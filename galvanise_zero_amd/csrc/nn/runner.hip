@@ -53,6 +53,12 @@ struct Pool {
     // generation roll with per-pool filters: clear this pool's duplicate filter just before its
     // engine thread delivers batch `clear_at` (its first batch on the new network); -1: none
     std::atomic<long> clear_at{-1};
+    // set by the pool's engine thread once gz_pool_start has returned.  gz_pool_start builds the pool's
+    // vectors of games with push_back; statistics read from another thread walk those vectors, so a
+    // stats call right after gz_runner_start walked a vector that was being moved (freed memory: a
+    // segmentation fault on the large configurations, whose games take longest to create).  Until the
+    // flag is set the pool counts as what it is: no game started, every counter zero.
+    std::atomic<bool> games_started{false};
 };
 
 // A launch is a list of parts: rows [row0, row0 + rows) of a pool's batch.  A pool's batch may be
@@ -185,7 +191,10 @@ static void engine_main(gz_runner* r, int tid) {
     const int P = r->cfg.pools_per_thread;
     std::vector<int> mine;
     for (int k = 0; k < P; ++k) mine.push_back(tid * P + k);
-    for (int i : mine) gz_pool_start(r->pools[i].pool, &r->conf);
+    for (int i : mine) {
+        gz_pool_start(r->pools[i].pool, &r->conf);
+        r->pools[i].games_started.store(true, std::memory_order_release);
+    }
     int idle = 0;
     using clk = std::chrono::steady_clock;
     clk::time_point idle_since{};
@@ -1014,7 +1023,7 @@ extern "C" int gz_runner_stats_get(gz_runner* r, gz_runner_stats* out) {
     out->samples = r->samples_taken.load();
     out->segments = r->segments.load();
     for (Pool& p : r->pools) {
-        if (!p.pool) continue;
+        if (!p.pool || !p.games_started.load(std::memory_order_acquire)) continue;
         gz_pool_stats s;
         gz_pool_get_stats(p.pool, &s);   // counters are plain longs written by the owning thread
         out->games_completed += s.games_completed;
@@ -1162,7 +1171,7 @@ extern "C" int gz_runner_ordinal_stats(gz_runner* r, gz_ordinal_stats* out) {
     }
     std::memset(out, 0, sizeof(*out));
     for (Pool& p : r->pools)
-        if (p.pool && gz_pool_add_ordinal_stats(p.pool, out) != 0) {
+        if (p.pool && p.games_started.load(std::memory_order_acquire) && gz_pool_add_ordinal_stats(p.pool, out) != 0) {
             g_err = gz_engine_last_error();
             return -1;
         }

@@ -10,7 +10,8 @@ oracle (oracle/nn_ref.forward) snapped to the lattice, and faulty_logits applies
 to the oracle side so that the CPU suite can show the comparison would notice it (faulty_se_logits:
 the slips of a squeeze-excite kernel; faulty_head_logits: those of the dense heads, with
 head_liveness, the conditions under which no output of a launch could pass against an untouched or
-a neighbour's buffer).
+a neighbour's buffer; faulty_input_logits: the slips of plane staging, im2col and the initial conv,
+on nets built with cover_initial, whose every (tap, plane) place initial_liveness shows to count).
 
 How the BN fold is made exact: galvanise_zero_amd/csrc/nn/weight_image.h fold_element computes
 scale = gamma / sqrt(fl32(var + 1e-3f)) in float32.  exact_vars() searches the float32 var for which
@@ -196,7 +197,7 @@ def _se_gating(rng, shape, K, mute, twin):
     return a
 
 
-def lattice_weights(desc, seed, *, nnz, wmax, wide=None, se=None):
+def lattice_weights(desc, seed, *, nnz, wmax, wide=None, se=None, cover_initial=False):
     """Weights in weight_spec order on which the forward is exact.
 
     Conv kernels: sparse, nnz signed integers of up to wmax per 3 x 3 (initial) output channel at
@@ -228,8 +229,20 @@ def lattice_weights(desc, seed, *, nnz, wmax, wide=None, se=None):
     quarter of them and none from a muted unit, so that every gate is sigmoid(+-K hid) or
     sigmoid(0): 0, 1/2 or 1 exactly once K hid is large (module docstring).
 
+    cover_initial: every (tap, plane) place of the initial conv is read, and nothing downstream can
+    hide it wholesale.  Place j (= tap * C + plane, the im2col row's k) gets a +1 towards output
+    channel j mod F, in the place of whatever sparse entry stood there; the initial BN's mean is 0
+    and its beta nnz * wmax or one more, which the sparse entries of a channel (at most nnz of them,
+    wmax each, on 0 / 1 planes, under a scale of at most 1) cannot outweigh, so the relu behind the
+    initial conv is the identity and every output channel is linear in the planes; policy 0's two
+    1 x 1 conv outputs read complementary halves of the trunk's channels, so every channel reaches
+    a head.  (Needs an initial BN, no conv biases, no wide operands; initial_liveness measures what
+    the later relus still hide.)
+
     leaky_relu, and se_units > 0 without `se`, are refused (module docstring)."""
     assert not desc.leaky_relu, "0.03 is not dyadic"
+    if cover_initial:
+        assert not wide and se is None and not desc.conv_bias and (desc.initial_bn or not desc.resnet_v2), "cover_initial: plain nets with an initial BN"
     assert not desc.se_units or se is not None, "the squeeze-excite gate is a sigmoid: only with saturating gates (se=...)"
     if se is not None:
         assert desc.se_units and desc.resnet_v2 and sig_bits(float(se["K"])) == 1, se
@@ -287,6 +300,13 @@ def lattice_weights(desc, seed, *, nnz, wmax, wide=None, se=None):
                 # stream each: a slip in any trunk channel then reaches a logit)
                 dense_head = head and kind != "policy_dense"
                 k = _sparse(rng, shape, shape[2] // 2 if dense_head else (2 * nnz if head else nnz), wmax, True)
+            if cover_initial and name == "initial_conv":
+                places = int(np.prod(shape[:-1]))
+                k.reshape(places, n)[np.arange(places), np.arange(places) % n] = 1.0
+            if cover_initial and name == "policy0_conv":      # output 1 reads the channels that output 0 leaves out
+                rest = np.nonzero(k[0, 0, :, 0] == 0)[0]
+                k[0, 0, :, 1] = 0.0
+                k[0, 0, rest, 1] = rng.integers(1, wmax + 1, size=rest.size) * rng.choice((-1, 1), size=rest.size)
             if se is not None and name.startswith("res") and name.endswith("_conv2") and sig_bits(float(desc.hw)) == 1:
                 c1, c2 = rng.choice(n, size=2, replace=False)
                 k[..., c2] = k[..., c1]
@@ -306,12 +326,16 @@ def lattice_weights(desc, seed, *, nnz, wmax, wide=None, se=None):
         elif name.endswith("_beta"):
             if sp == "beta":
                 a = stream_base = wide_values(n, False)
+            elif cover_initial and prefix == "initial_bn":
+                a = nnz * wmax + rng.integers(0, 2, size=n)
             elif sp == "plain":
                 a = rng.integers(-1, 2, size=n)
             else:
                 a = np.zeros(n)
         elif name.endswith("_mean"):
-            if sp == "w0":
+            if cover_initial and prefix == "initial_bn":
+                a = np.zeros(n)
+            elif sp == "w0":
                 a = last_conv.sum(axis=(0, 1, 2)) - 32.0 - np.arange(n) % 16
             elif isinstance(sp, tuple):      # the A of the stream channel each output reads
                 a = stream_base[np.argmax(last_conv.sum(axis=(0, 1)), axis=0)] - sp[1]
@@ -495,11 +519,13 @@ def _forward(desc, weights, planes, tap=None, hooks=None, se_fault=None, se_stri
 
     def conv(x, name, bn, kind, skip=None):
         k = w[name].astype(np.float64)
-        wrap = False
+        wrap, y = False, None
         if name in hooks:
-            x, k, wrap = hooks[name](x, k)
+            x, k, wrap, *y = hooks[name](x, k)     # (a fourth item: the conv's output itself, faulty_input_logits)
+            y = y[0] if y else None
         tap(kind, name, x, k, bn, skip)
-        y = _conv(x, k, wrap)
+        if y is None:
+            y = _conv(x, k, wrap)
         if desc.conv_bias:
             y = y + w[name + "_bias"].astype(np.float64)
         return nn_ref._bn(y, w, bn) if bn else y
@@ -890,6 +916,147 @@ def faulty_logits(desc, weights, planes, fault, conv, bits=8):
             assert fault == "wrap_pad", fault
         return inp, k, fault == "wrap_pad"
     return _forward(desc, weights, planes, hooks={conv: hook})[0]
+
+
+# ---- the input path: plane staging, im2col, the initial conv ---------------------------------------------
+def input_planes(desc, n, seed):
+    """[n, C, H, W] float32 planes of 0 / 1, every cell of every plane set with probability 1/2 on its
+    own (random_planes leaves whole planes of a board empty, and a place of the initial conv that
+    reads an empty plane cannot show); the last cell of every board is set, so that the last float4
+    of its plane block holds something."""
+    rng = np.random.default_rng([seed, 31])
+    x = (rng.random((n, desc.input_channels, desc.input_columns, desc.input_rows)) < 0.5).astype(np.float32)
+    x[:, -1, -1, -1] = 1.0
+    return x
+
+
+def initial_places(desc):
+    """[(tap, plane)] of the initial conv in the order of the im2col row's k = tap * C + plane."""
+    return [(t, c) for t in range(desc.initial_kernel ** 2) for c in range(desc.input_channels)]
+
+
+def initial_k0(desc):
+    """The im2col row's length: the places rounded up to the initial GEMM's k-step of 32."""
+    return (len(initial_places(desc)) + 31) // 32 * 32
+
+
+def initial_liveness(desc, weights, planes):
+    """The (tap, plane) places of the initial conv whose removal -- every weight of the place set to
+    zero -- moves no expected logit on these planes: what a slip confined to that place could do
+    unseen.  Empty: the comparison sees the whole initial conv.  (A place that no weight reads is
+    dead by definition.)"""
+    base = _forward(desc, weights, planes)[0]
+    k0 = dict(weights)["initial_conv"]
+    dead = []
+    for j, place in enumerate(initial_places(desc)):
+        k = k0.copy()
+        k.reshape(-1, k.shape[3])[j] = 0.0
+        if np.array_equal(k, k0):
+            dead.append(place)
+            continue
+        got = _forward(desc, [(n, k if n == "initial_conv" else a) for n, a in weights], planes)[0]
+        if all(np.array_equal(g, b) for g, b in zip(got, base)):
+            dead.append(place)
+    return dead
+
+
+def _im2col(desc, planes):
+    """The initial conv as the kernels run it: (rows [N, npos, K0] with k = tap * C + plane, zero
+    beyond the places and at off-board taps; the weights as [K0, F] taken from `k`, by a function)."""
+    N, C, H, W = planes.shape
+    ks = desc.initial_kernel
+    pad = ks // 2
+    xp = np.pad(planes.astype(np.float64), ((0, 0), (0, 0), (pad, pad), (pad, pad)))
+    taps = [np.transpose(xp[:, :, dy:dy + H, dx:dx + W], (0, 2, 3, 1)).reshape(N, H * W, C) for dy in range(ks) for dx in range(ks)]
+    im = np.concatenate(taps, axis=2)
+    K0 = initial_k0(desc)
+    im = np.pad(im, ((0, 0), (0, 0), (0, K0 - im.shape[2])))
+
+    def matrix(k):
+        return np.pad(k.astype(np.float64).reshape(-1, k.shape[3]), ((0, K0 - ks * ks * C), (0, 0)))
+    return im, matrix
+
+
+INPUT_FAULTS = ("swizzle_spill", "chunk_swap", "drop_tail_float4", "neighbour_board_planes", "shifted_row", "pad_reads_next_tap")
+
+
+def input_fault_applies(desc, fault, rows):
+    """Where the geometry lets an input fault occur: the old swizzle spills only where some chunk
+    index XORed with a position's low bits leaves the row; a neighbour's planes need a second board; padded k exist only where
+    the places are no multiple of 32.  The others occur everywhere."""
+    assert fault in INPUT_FAULTS, fault
+    nch = initial_k0(desc) // 8
+    if fault == "swizzle_spill":      # (no power of two, and no multiple of 16 either: 12, 20, 24, 28, 36 chunks of the sweep)
+        m = min(nch, 16) - 1
+        return any(j ^ (p & m) >= nch for j in range(nch) for p in range(16))
+    if fault == "neighbour_board_planes":
+        return rows >= 2
+    if fault == "pad_reads_next_tap":
+        return initial_k0(desc) > len(initial_places(desc))
+    return True
+
+
+def faulty_input_logits(desc, weights, planes, fault, offset=None):
+    """The logits of a forward whose input path slips the way a wrong kernel would (oracle side only):
+      swizzle_spill          forward_kernel.h's first chunk swizzle, restated: chunk j of position p's
+                             im2col row lies at chunk j ^ (p & (min(chunks, 16) - 1)) of the row; where
+                             that leaves the row it lands in position p + 1's row, and what is read
+                             back there is the chunk that position p + 1 itself put in that slot
+                             (behind the last position: the zero row)
+      chunk_swap             chunk 0 and the last chunk that holds a place (if that is chunk 0: chunk 1) change places in every row
+      drop_tail_float4       the last four floats of every board's plane block read as zero
+      neighbour_board_planes boards 2k + 1 read board 2k's planes (a workgroup's second board, the first's)
+      shifted_row            every board's plane block is read from its address rounded down to 16
+                             bytes, the launch's planes lying `offset` floats (default 1) behind a
+                             16-byte boundary, with zeros in front
+      pad_reads_next_tap     the row's padding k = places .. K0 - 1 holds the row's first entries over
+                             again instead of zeros, and the weights there are +1 (towards channel
+                             k mod F) instead of zero"""
+    assert fault in INPUT_FAULTS, fault
+    N = planes.shape[0]
+    block = planes[0].size
+    x = planes.astype(np.float64).copy()
+    if fault == "drop_tail_float4":
+        x.reshape(N, -1)[:, -4:] = 0.0
+    elif fault == "neighbour_board_planes":
+        x[1::2] = x[0:N - 1:2][:len(x[1::2])]
+    elif fault == "shifted_row":
+        off = 1 if offset is None else offset
+        flat = np.concatenate([np.zeros(off), x.reshape(-1), np.zeros(4)])
+        x = np.stack([flat[(off + b * block) // 4 * 4:][:block] for b in range(N)]).reshape(x.shape)
+    im, matrix = _im2col(desc, x)
+    nch, places = im.shape[2] // 8, len(initial_places(desc))
+
+    def hook(inp, k):
+        w0 = matrix(k)
+        assert fault in ("drop_tail_float4", "neighbour_board_planes", "shifted_row") or np.array_equal(im @ w0, nn_ref._conv_same(inp, k).reshape(N, -1, k.shape[3]))
+        rows = im
+        if fault == "swizzle_spill":
+            m = min(nch, 16) - 1
+            npos = im.shape[1]
+            ch = np.concatenate([im, np.zeros((N, 1, im.shape[2]))], axis=1).reshape(N, npos + 1, nch, 8)
+            rows = np.zeros((N, npos, nch, 8))
+            for p in range(npos):
+                for j in range(nch):
+                    at = j ^ (p & m)
+                    theirs = (at - nch) ^ ((p + 1) & m)      # the chunk position p + 1 keeps in that slot
+                    if at >= nch and p + 1 == npos:
+                        rows[:, p, j] = 0.0
+                    else:
+                        rows[:, p, j] = ch[:, p + 1, theirs] if (at >= nch and theirs < nch) else ch[:, p, j]
+            rows = rows.reshape(im.shape)
+        elif fault == "chunk_swap":
+            b = (places - 1) // 8
+            a = 0 if b else 1       # (a single chunk of places: with the padding chunk behind it)
+            rows = im.reshape(N, -1, nch, 8).copy()
+            rows[:, :, [a, b]] = rows[:, :, [b, a]]
+            rows = rows.reshape(im.shape)
+        elif fault == "pad_reads_next_tap":
+            rows, w0 = im.copy(), w0.copy()
+            rows[:, :, places:] = im[:, :, :im.shape[2] - places]
+            w0[np.arange(places, im.shape[2]), np.arange(places, im.shape[2]) % k.shape[3]] = 1.0
+        return inp, k, False, (rows @ w0).reshape(N, desc.input_columns, desc.input_rows, k.shape[3])
+    return _forward(desc, weights, x.astype(np.float32), hooks={"initial_conv": hook})[0]
 
 
 # ---- the dense heads: faults on the oracle side only -------------------------------------------------

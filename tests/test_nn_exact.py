@@ -4,7 +4,10 @@ check_representable); the nets are alive; and the comparison would notice a wron
 kernel-like slip, applied to the oracle side alone, moves at least one expected logit.  For the
 squeeze-excite nets that includes the saturation conditions (every gate exactly 0, 1/2 or 1), gates
 that take all three values and differ between the boards of a launch, and the slips a squeeze-excite
-kernel can make (exact_lattice.SE_FAULTS).  For the dense-heads nets (HEAD_CASES): no output of a
+kernel can make (exact_lattice.SE_FAULTS).  For the input-path nets (tests/test_nn_input_exact_gpu.py):
+no (tap, plane) place of the initial conv can be removed without moving a logit of the first row
+(exact_lattice.initial_liveness), and each slip of plane staging and im2col (exact_lattice.INPUT_FAULTS)
+moves one.  For the dense-heads nets (HEAD_CASES): no output of a
 launch is zero where an untouched buffer would pass, and each slip a heads kernel can make
 (exact_lattice.HEAD_FAULTS) moves a logit wherever the net's geometry lets it occur.  No GPU."""
 import dataclasses
@@ -17,6 +20,8 @@ from galvanise_zero_amd.nn.desc import NetDesc
 from oracle import nn_ref
 from test_nn_exact_gpu import (ALL, CASES, CHUNKED, HEAD_CASES, HEAD_CHUNKED, HEAD_LARGE_VARIANTS, HEAD_NO_GEMM, HEAD_VARIED,
                                LARGE_ROWS, PROBABILITY, SAT, SATURATED, SCALES, SE_CASES, SE_VARIED, _softmax64, build, saturated)
+from test_nn_input_exact_gpu import CASES as INPUT_CASES, EDGE_FITS, EDGE_OVER, FUSED, LARGE_ROWS as INPUT_LARGE_ROWS, LAYERED
+from test_nn_input_exact_gpu import REFUSED as INPUT_REFUSED, build as input_build
 
 FAMILIES = {c.family: name for name, c in CASES.items() if c.family}
 GEOMETRY_FAULTS = ("tap_swap", "wrap_pad", "channel_swap", "drop_last_channel")
@@ -390,6 +395,98 @@ def test_saturated_conditions(name, mode, tie):
         assert np.array_equal(_softmax64(z), p), (name, i)
         low = np.where(p > 0, -np.inf, z).max(axis=1)
         assert (z.max(axis=1) - low >= SAT / 2).all()
+
+
+# ---- the input path (tests/test_nn_input_exact_gpu.py) -------------------------------------------------
+def _input_fault_rows(fault):
+    return 2 if fault == "neighbour_board_planes" else 1
+
+
+@pytest.mark.parametrize("name", sorted(INPUT_CASES))
+def test_input_conditions(name):
+    """check_representable holds in every mode the GPU file runs the case in, at its 5 rows."""
+    desc, w, x, _ = input_build(name)
+    assert x.shape[0] == 5 and INPUT_CASES[name].modes
+    for mode in INPUT_CASES[name].modes:
+        xl.check_representable(desc, w, x, mode)
+
+
+def test_input_conditions_at_the_large_launch():
+    for name in (EDGE_FITS, EDGE_OVER):
+        desc, w, x, _ = input_build(name, INPUT_LARGE_ROWS)
+        assert x.shape[0] == INPUT_LARGE_ROWS
+        xl.check_representable(desc, w, x, "bf16x3")
+
+
+@pytest.mark.parametrize("name", sorted(INPUT_CASES))
+def test_input_liveness(name):
+    """Every (tap, plane) place of the initial conv is read, and removing any one of them moves an
+    expected logit of the first row alone (hence of every launch, which all hold that row); the
+    relu behind the initial conv is the identity there (cover_initial), and every trunk channel is
+    read by one of policy 0's two conv outputs."""
+    desc, w, x, expected = input_build(name)
+    k = dict(w)["initial_conv"]
+    places = xl.initial_places(desc)
+    assert k.shape[0] == desc.initial_kernel and len(places) == k[..., 0].size and (k.reshape(len(places), -1) != 0).any(axis=1).all()
+    assert (k.reshape(len(places), -1)[np.arange(len(places)), np.arange(len(places)) % k.shape[3]] == 1).all()
+    assert ((dict(w)["policy0_conv"][0, 0] != 0).sum(axis=1) == 1).all()
+    assert xl.initial_liveness(desc, w, x[:1]) == []
+    assert xl.trunk_alive(desc, w, x) >= 0.30
+    for z in expected[:-1]:
+        assert len(np.unique(z)) >= 32 and len(np.unique(z, axis=0)) == x.shape[0]
+
+
+def test_input_liveness_names_a_dead_place():
+    """initial_liveness on a net without the cover (the generator's two weights per channel): places
+    that nothing reads, and places that are read and hidden, are named."""
+    desc, _, x, _ = input_build("in_8x8_c24_f128")
+    w = xl.lattice_weights(desc, 1, nnz=2, wmax=1)
+    k = dict(w)["initial_conv"]
+    unread = [pl for j, pl in enumerate(xl.initial_places(desc)) if not k.reshape(-1, k.shape[3])[j].any()]
+    dead = xl.initial_liveness(desc, w, x[:1])
+    assert unread and set(unread) < set(dead)
+
+
+@pytest.mark.parametrize("name,fault", [(name, fault) for name in sorted(INPUT_CASES) for fault in xl.INPUT_FAULTS])
+def test_input_fault_is_seen(name, fault):
+    """Each slip an input path can make, on the oracle side alone, moves an expected logit of the first
+    row (a neighbour's planes: of the first two) on every case whose geometry lets it occur."""
+    desc, w, x, expected = input_build(name)
+    rows = _input_fault_rows(fault)
+    if not xl.input_fault_applies(desc, fault, rows):
+        return
+    assert _differs(xl.faulty_input_logits(desc, w, x[:rows], fault), [e[:rows] for e in expected]), (name, fault)
+
+
+@pytest.mark.parametrize("offset", (1, 2, 3))
+def test_input_shifted_row_at_every_offset(offset):
+    """A plane block 4, 8 or 12 bytes behind a 16-byte boundary, read from the boundary."""
+    desc, w, x, expected = input_build(EDGE_FITS)
+    assert _differs(xl.faulty_input_logits(desc, w, x[:1], "shifted_row", offset=offset), [e[:1] for e in expected])
+
+
+def test_input_cases_cover_the_parameter_space():
+    """Every chunk count from 4 to 36 in both fused modes on two fused geometries at least; the swizzle
+    that once spilled occurs at 12, 20, 24, 28 and 36 chunks (K0 = 96, 160, 224 among them) and the fault
+    is seen there at one row (test_input_fault_is_seen); both sides of the gather's padding in the four
+    layered modes; a 1 x 1 initial conv; plane blocks off alignment and above the prefetch's cap; at
+    most one refused case per chunk count."""
+    chunks = lambda d: xl.initial_k0(d) // 8
+    for n in range(4, 37, 4):
+        for mode in FUSED:
+            geos = {(c.desc.hw, c.desc.cnn_filter_size) for c in INPUT_CASES.values() if chunks(c.desc) == n and mode in c.modes
+                    and c.desc.initial_kernel == 3}
+            assert len(geos) >= 2, (n, mode, geos)
+    spills = {n for n in range(4, 37, 4) if xl.input_fault_applies(NetDesc(8 * n // 9, 8, 8, 64, 1, [9]), "swizzle_spill", 1)}
+    assert spills == {12, 20, 24, 28, 36}
+    assert {xl.initial_k0(c.desc) for c in INPUT_CASES.values() if c.desc.initial_kernel == 3} >= {96, 160, 224}
+    layered = {c.desc.input_channels for c in INPUT_CASES.values() if set(LAYERED) <= set(c.modes) and c.desc.initial_kernel == 3}
+    assert layered >= {15, 16, 17, 33}
+    assert {c.desc.input_channels for c in INPUT_CASES.values() if c.desc.initial_kernel == 1} == {3, 32, 33}
+    blocks = {c.desc.input_channels * c.desc.hw for c in INPUT_CASES.values()}
+    assert any(b % 4 for b in blocks) and any(b % 4 == 0 and b > 4096 for b in blocks)
+    refused = [chunks(d) for d, _ in INPUT_REFUSED.values()]
+    assert len(refused) == len(set(refused)) <= 3
 
 
 def test_heads_path_bits_match_the_header():
